@@ -20,7 +20,14 @@ built from the same sources (sha256 of csrc/ + header) on the same workload; nul
 cpu_baseline: the C oracle (oracle/ssnt_oracle.c, same split-exponent arithmetic; the reference
 has no forward-backward) on this host's cores, rank 0 at N=1 only.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line (headline value,
+ms_per_step and the roofline figures, which come from the same K launches). --full adds what
+takes runs of its own: the status / loss-sum check through the Python mirror before the timed
+region, e2e_host, cpu_baseline and, for N > 1, per_step_allreduce.
+--dump-outputs DIR writes what the last timed step left in the caller's buffers (loss, grad,
+loss_sum) as DIR/<name>.npy; the inputs depend only on the arguments (seed = rank).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
        (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
 """
 import argparse
@@ -41,6 +48,7 @@ import ssnt_tts_amd as S  # noqa: E402
 BASELINE = json.loads((ROOT / "BASELINE.json").read_text())
 PEAK_HBM_GBS = 8000.0
 BYTES_PER_CELL = 16
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
 
 
 def synth(B, T, U, seed, dev):
@@ -190,6 +198,25 @@ def pmc_traffic(kernel, source_sha, B, T, U):
     return d.get("hbm_bytes_per_launch"), f"profiles/{d.get('tag')}_fwd_bwd_summary.json"
 
 
+def dump_outputs(path, out, loss_sum):
+    """Write the last timed step's outputs as float32 .npy files: loss (B), grad (B,T,U,2) and
+    loss_sum (1). An array that would take the total past DUMP_LIMIT_BYTES is written as a fixed
+    sample instead: the elements at `<name>_index.npy` (sorted flat indices, seed 0)."""
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    left = DUMP_LIMIT_BYTES
+    for name, t in (("loss_sum", loss_sum), ("loss", out["loss"]), ("grad", out["grad"])):
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.nbytes > left:
+            n = left // 12  # 4 B value + 8 B index per sampled element
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            np.save(path / f"{name}_index.npy", idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+            left -= 8 * n
+        np.save(path / f"{name}.npy", a)
+        left -= a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -198,8 +225,13 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="utterances per GPU")
     ap.add_argument("--T", type=int, default=200)
     ap.add_argument("--U", type=int, default=80)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-pointer e2e_host figure")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not "
+                    "need: the mirror check, e2e_host, cpu_baseline, per_step_allreduce (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, "
+                    "grad and loss_sum as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the host-pointer "
+                    "e2e_host figure")
     ap.add_argument("--variant", type=int, default=0, help="fwd-bwd kernel variant (A/B build, "
                     "include/ssnt_tts_c_ab.h): 0 the product's dispatch, 1 two-wave, 2 segmented")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL); gloo only to rehearse "
@@ -230,11 +262,11 @@ def main():
            "status": torch.zeros(1, dtype=torch.int32, device=dev),
            "loss_sum": torch.zeros(1, device=dev)}
 
-    # correctness/status check once through the full Python mirror, outside the timed region
-    r = S.ssnt_fwd_bwd(lt, sl, pl, out=out, check=True, loss_sum=True)
-    kernel = S.last_fwd_bwd_kernel()  # the instance the timed launches dispatch (same shapes)
-    assert torch.isfinite(r["loss"]).all()
-    assert torch.isclose(r["loss_sum"], r["loss"].double().sum().float(), rtol=1e-5).all()
+    if args.full:
+        # correctness/status check once through the full Python mirror, outside the timed region
+        r = S.ssnt_fwd_bwd(lt, sl, pl, out=out, check=True, loss_sum=True)
+        assert torch.isfinite(r["loss"]).all()
+        assert torch.isclose(r["loss_sum"], r["loss"].double().sum().float(), rtol=1e-5).all()
 
     # The timed loop calls the C ABI directly (pointers bound once). N=1 and N>1 run the same
     # loop: the K steps are one HIP graph of K launches (the host issues nothing per step), each
@@ -268,6 +300,7 @@ def main():
     with torch.cuda.graph(graph, stream=cap):
         for k in range(K):
             launch(cap, k)
+    kernel = S.last_fwd_bwd_kernel()  # the instance the timed launches dispatch
     graph.replay()  # first replay uploads the graph (untimed)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -288,8 +321,10 @@ def main():
         elapsed, kern_ms = float(t[0]), float(t[1])
         # every step's reduced sum is the global batch loss (one shard per rank)
         assert torch.isfinite(sums).all()
+    if args.dump_outputs and rank == 0:  # before anything else writes the output buffers
+        dump_outputs(args.dump_outputs, out, sums[K - 1:K])
     per_step = None
-    if dist:
+    if dist and args.full:
         # The same K steps with one all-reduce of each step's loss sum right after it (RCCL on a
         # side stream, overlapped with the next step's kernel) -- the per-step synchronisation a
         # training loop that reduces every step's loss pays. Reported beside the headline, which
@@ -317,9 +352,9 @@ def main():
                 "note": "one RCCL all-reduce per step on a side stream, steps launched one by "
                         "one from the host (the headline value amortises one all-reduce of the "
                         "K per-step sums over a K-launch graph)"}
-        if world == 1 and not args.no_e2e:
+        if args.full and world == 1 and not args.no_e2e:
             res["e2e_host"] = e2e_host(B, T, U, lt, out["loss"])
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(B, T, U)
         print(json.dumps(res), flush=True)
     if dist:

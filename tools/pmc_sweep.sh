@@ -12,7 +12,7 @@ for grp in "$@"; do
   OUT=$ROOT/gpurun_out/pmc_$TAG/$i
   mkdir -p "$OUT"
   timeout -k 10 180 rocprofv3 --pmc $grp --output-format csv -d "$OUT" -o p -- \
-    python3 "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/log.txt" 2>&1
+    python3 "$ROOT/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/log.txt" 2>&1
   i=$((i+1))
 done
 python3 "$ROOT/tools/pmc_table.py" "$ROOT/gpurun_out/pmc_$TAG"
