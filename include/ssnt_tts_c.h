@@ -172,6 +172,26 @@ int ssnt_fwd_bwd(const float *log_trans, const float *log_obs, const int *step_l
                  float *loss, float *grad_trans, float *grad_obs, float *log_alpha,
                  float *log_beta);
 
+/* ---- exact best path (Viterbi) on the emit/shift lattice ----
+ * The max-plus recurrence over the tensors of ssnt_fwd_bwd_device, IEEE f32 adds and compares in
+ * the order DESIGN.md 2.2 states (a tie keeps the emit), so the outputs are bit-identical to a
+ * plain f32 restatement. log_prob (B) = log-probability of the most probable monotone alignment
+ * (with the terminal emit under SSNT_FLAG_TERMINAL_EMIT, the only flag accepted); position (B,T)
+ * = the input position of every step on that path (-1 for steps >= S_b; NULL = skip); duration
+ * (B,U) = the number of steps each position holds (0 for positions >= P_b; NULL = skip). An
+ * infeasible utterance (S_b < P_b, S_b = 0, P_b = 0, log_prob = -inf, or a length beyond the
+ * tensor, which also sets SSNT_ERR_BAD_LENGTH in `status`) gets log_prob -inf, positions -1 and
+ * durations 0. -inf inputs are legal. max_pos > 1024 returns SSNT_ERR_UNSUPPORTED. `workspace`
+ * holds ssnt_viterbi_align_workspace_size() bytes: 0 (NULL workspace) while the backpointer bits
+ * of one utterance fit LDS; with position and duration both NULL no backpointers are kept and
+ * no workspace is needed. Device pointers, asynchronous on `stream` (a hipStream_t). New: the
+ * reference only searches this lattice with a pruned beam. */
+size_t ssnt_viterbi_align_workspace_size(int batch, int max_steps, int max_pos);
+int ssnt_viterbi_align_device(const float *log_trans, const float *log_obs, const int *step_len,
+                              const int *pos_len, int batch, int max_steps, int max_pos, int flags,
+                              float *log_prob, int *position, int *duration, void *workspace,
+                              size_t workspace_bytes, int *status, void *stream);
+
 /* ---- F4: v2 duration-class (semi-Markov) forward-backward (DESIGN.md
  * "Duration lattice"). New: the reference only decodes this lattice; the move rules are the v2
  * decode's (src/v2.rs:94-166 -- band, overrun, exact final total, zero-duration class; test_mode

@@ -780,6 +780,23 @@ int ssnt_fwd_bwd_sum_device(const float* log_trans, const float* log_obs, const 
   return launch_fwd_bwd(a, as_stream(stream));
 }
 
+size_t ssnt_viterbi_align_workspace_size(int batch, int max_steps, int max_pos) {
+  if (batch <= 0 || max_steps <= 0 || max_pos <= 0 || max_pos > 1024) return 0;
+  return viterbi_workspace_bytes(batch, max_steps, max_pos);
+}
+
+int ssnt_viterbi_align_device(const float* log_trans, const float* log_obs, const int* step_len,
+                              const int* pos_len, int batch, int max_steps, int max_pos, int flags,
+                              float* log_prob, int* position, int* duration, void* workspace,
+                              size_t workspace_bytes, int* status, void* stream) {
+  ViterbiArgs a{};
+  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
+  a.B = batch; a.T = max_steps; a.U = max_pos; a.flags = flags;
+  a.log_prob = log_prob; a.position = position; a.duration = duration;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  return launch_viterbi(a, as_stream(stream));
+}
+
 size_t ssnt_v2_fwd_bwd_workspace_size(int batch, int max_steps, int max_total, bool test_mode) {
   return v2_fwd_bwd_workspace_bytes(batch, max_steps, max_total, test_mode);
 }

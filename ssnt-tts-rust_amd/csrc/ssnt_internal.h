@@ -78,6 +78,23 @@ int diag_read(void* host, size_t bytes);  // -DSSNT_DIAG builds only (tools/diag
 void note_fwd_bwd_dispatch(const char* fmt, ...);
 const char* last_fwd_bwd_dispatch();
 
+// ---- exact best path on the emit/shift lattice (viterbi.hip) ----
+struct ViterbiArgs {
+  const float* log_trans;  // (B,T,U,2)
+  const float* log_obs;    // (B,T,U) or null
+  const int* step_len;     // (B)
+  const int* pos_len;      // (B)
+  int B, T, U, flags;
+  float* log_prob;   // (B)
+  int* position;     // (B,T) or null
+  int* duration;     // (B,U) or null
+  void* workspace;   // backpointer bits when they do not fit LDS
+  size_t workspace_bytes;
+  int* status;
+};
+size_t viterbi_workspace_bytes(int B, int T, int U);
+int launch_viterbi(const ViterbiArgs& a, hipStream_t stream);
+
 // ---- F4: v2 duration-class forward-backward (v2_fwd_bwd.hip) ----
 struct V2FwdBwdArgs {
   const float* logits;       // (B, Imax, D) per-step class log-probs

@@ -1,0 +1,482 @@
+// viterbi.hip -- exact best path (Viterbi) over the emit/shift lattice for gfx950.
+//
+// Semantics: DESIGN.md 2.2. A max-plus sweep over the (B,T,U,2) tensor of the forward-backward:
+// f32 adds and one strict compare per cell, no reassociation, so every form is bit-identical to
+// the plain f32 restatement (tests/viterbi_ref.py). One workgroup = one utterance, 5 waves:
+//
+//   wave 0      the chain: V[s][p] for s = 1..S-1. A lane holds K consecutive positions
+//               (p = K*lane + k, K = 1..16, so one wave spans U <= 1024 and no row needs a
+//               cross-wave neighbour); the left neighbour of k = 0 is one DPP wave shift. The
+//               compare of each k lands in an SGPR pair, which is that step's 64-bit backpointer
+//               word (bit `lane` of word k <-> position K*lane + k).
+//   waves 1..4  loaders: the rows of the next chunk (R rows) go global -> registers while the
+//               chain sweeps the current chunk, then registers -> LDS, transposed to [row][k][lane]
+//               (k-planes padded by 32/K so both the loaders' writes and the chain's reads are
+//               bank-conflict free). Two LDS buffers, one workgroup barrier per chunk: the load
+//               latency of a chunk hides behind R chain steps. The loads are range-checked
+//               buffer loads, all issued back to back (no predicate, so no wait between them).
+//
+// Backpointer words: T*K*8 bytes per utterance, in LDS when they fit beside the buffers, else in
+// the caller's workspace (staged through LDS, flushed 64 rows at a time with vector stores, and
+// read back for the backtrace in blocks as large as the two chunk buffers, which are free by
+// then). With no path output nothing is kept.
+//
+// Backtrace, same launch: the path is monotone, so wave 0 walks it by runs: 64 lanes test the
+// bit of the current position at 64 consecutive steps, one ballot finds the step that entered
+// the position. At most (P-1) + S/64 LDS round trips instead of S. start[p] (the first step at
+// p) then gives duration[p] = start[p+1] - start[p] and position[s] by a binary search, both
+// written by all waves.
+#include <hip/hip_runtime.h>
+
+#include <utility>
+
+#include "lattice_dev.h"
+
+namespace ssnt {
+namespace {
+
+constexpr int kVitLoaders = 4;                        // loader waves
+constexpr int kVitThreads = 64 * (1 + kVitLoaders);
+constexpr int kVitUnits = 16;                         // load units per loader lane and chunk
+constexpr int kVitMaxRpw = 8;                         // rows per loader wave and chunk, at most
+constexpr int kVitStageRows = 64;                     // workspace mode: rows staged per flush
+constexpr int kVitJunk = 160;                         // elements behind each buffer: unused units' writes
+constexpr size_t kVitHeadBytes = 64;
+constexpr int kVitNoUnit = 0x7fffffff;                // byte offset no buffer range contains
+
+// shr1 (lattice_dev.h) with -inf for lane 0: the lane without a source keeps `old`. No select on
+// the lane index around it -- a DPP read of a lane that EXEC masks off counts as "no source", and
+// the compiler is free to turn such a select into exactly that mask.
+__device__ __forceinline__ float shr1_ninf(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp((int)0xff800000u, __builtin_bit_cast(int, x),
+                                                               0x138, 0xf, 0xf, false));
+}
+
+// v_writelane_b32: lane `lane` of the result holds the wave-uniform `v`, the other lanes keep `old`
+// (bound to the LLVM intrinsic by name, as buffer_ops.h does: this toolchain has no clang builtin)
+extern "C" __device__ int vit_writelane(int v, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>): unrolled in the source, so the
+// per-unit register arrays are split into scalars before any loop pass sees them
+template <class F, int... I>
+__device__ __forceinline__ void vit_each(F& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void vit_for(F f) {
+  vit_each(f, std::make_integer_sequence<int, N>{});
+}
+
+struct VitShared {
+  int feasible, s, p;
+};
+
+constexpr int vit_k(int U) { return U <= 64 ? 1 : U <= 128 ? 2 : U <= 256 ? 4 : U <= 512 ? 8 : 16; }
+constexpr int vit_kstride(int K) { return 64 + (K > 1 ? 32 / K : 0); }  // float2 / float units
+// Rows per chunk. A loader lane moves kVitUnits units per chunk: 16-byte units (two positions)
+// when log_trans is 16-byte aligned with even U and there is no log_obs, else one position per
+// unit (log_obs moves as single floats, so it sets the unit count whenever it is there).
+inline int vit_chunk_rows(int U, bool wide_units) {
+  const int per_row = wide_units ? (U + 127) / 128 : (U + 63) / 64;
+  int r = kVitUnits / per_row;
+  r = r < 1 ? 1 : r > kVitMaxRpw ? kVitMaxRpw : r;
+  return kVitLoaders * r;
+}
+struct VitLayout {
+  int K, R;
+  size_t start_off, lt_off, ob_off, bits_off, total;  // bytes
+};
+// mode: 0 no backpointers, 1 backpointer words in LDS, 2 in the workspace (stage rows)
+inline VitLayout vit_layout(int T, int U, int R, bool obs, int mode) {
+  VitLayout L{};
+  L.K = vit_k(U);
+  L.R = R;
+  const size_t buf = (size_t)R * L.K * vit_kstride(L.K) + kVitJunk;  // elements of one buffer
+  L.start_off = kVitHeadBytes;
+  L.lt_off = (L.start_off + (size_t)(U + 2) * 4 + 15) & ~(size_t)15;
+  L.ob_off = L.lt_off + 2 * buf * 8;
+  L.bits_off = L.ob_off + (obs ? 2 * buf * 4 : 0);
+  L.total = L.bits_off + (mode == 1 ? (size_t)T * L.K * 8
+                          : mode == 2 ? (size_t)kVitStageRows * L.K * 8 : 0);
+  return L;
+}
+// the deepest chunk the unit count gives, shortened until everything fits LDS
+inline VitLayout vit_pick(int T, int U, bool wide_units, bool obs, int mode) {
+  int R = vit_chunk_rows(U, wide_units);
+  VitLayout L = vit_layout(T, U, R, obs, mode);
+  while (L.total > kLdsBudget && R > kVitLoaders) {
+    R -= kVitLoaders;
+    L = vit_layout(T, U, R, obs, mode);
+  }
+  return L;
+}
+// The backpointer words stay in LDS when they fit beside the chunk buffers the log_obs form has
+// in workspace mode (from the shape alone: the query knows neither log_obs nor the alignment).
+inline bool vit_bits_fit(int T, int U) {
+  const int R = vit_pick(T, U, false, true, 2).R;
+  return vit_layout(T, U, R, true, 1).total <= kLdsBudget;
+}
+
+struct VitParams {
+  int R;
+  int vec;  // log_trans moves in 16-byte units (16-byte aligned, U even), else 8-byte
+  unsigned start_off, lt_off, ob_off, bits_off;
+};
+
+// MODE: 0 no path output (no backpointers), 1 backpointer words in LDS, 2 in the workspace
+template <int K, bool OBS, int MODE>
+__global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParams q) {
+  constexpr int kKs = vit_kstride(K);
+  constexpr int kRow = K * kKs;  // LDS row stride (float2 units for log_trans, floats for log_obs)
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63;
+  const int T = a.T, U = a.U, R = q.R;
+  const int S = a.step_len[b];
+  const int P = a.pos_len[b];
+  const size_t TU = (size_t)T * U;
+  const float* lt = a.log_trans + (size_t)b * TU * 2;
+  const float* lo = OBS ? a.log_obs + (size_t)b * TU : nullptr;
+  int* pos_out = (MODE && a.position) ? a.position + (size_t)b * T : nullptr;
+  int* dur_out = (MODE && a.duration) ? a.duration + (size_t)b * U : nullptr;
+  const float ninf = -__builtin_inff();
+
+  VitShared* sh = reinterpret_cast<VitShared*>(smem);
+  int* start = reinterpret_cast<int*>(smem + q.start_off);
+  float2* ltb = reinterpret_cast<float2*>(smem + q.lt_off);
+  float* obb = reinterpret_cast<float*>(smem + q.ob_off);
+  const int bufsz = R * kRow + kVitJunk;  // elements of one buffer
+  unsigned long long* bits = reinterpret_cast<unsigned long long*>(smem + q.bits_off);
+  unsigned long long* stage = bits;                          // workspace mode
+  // workspace mode, backtrace: the chunk buffers are free by then and hold 2 * bufsz / K rows
+  unsigned long long* wbuf = reinterpret_cast<unsigned long long*>(ltb);
+  const int walk_rows = 2 * bufsz / K;
+  unsigned long long* ws = MODE == 2 ? reinterpret_cast<unsigned long long*>(a.workspace) + (size_t)b * T * K
+                                     : nullptr;
+
+  auto fill_empty = [&]() {  // the infeasible rule: every position -1, every duration 0
+    if (pos_out)
+      for (int s = tid; s < T; s += kVitThreads) pos_out[s] = -1;
+    if (dur_out)
+      for (int p = tid; p < U; p += kVitThreads) dur_out[p] = 0;
+  };
+  if (!(S >= 1 && P >= 1 && S <= T && P <= U && S >= P)) {
+    if ((S > T || P > U || S < 0 || P < 0) && a.status && tid == 0) atomicOr(a.status, kStatusBadLength);
+    if (tid == 0) a.log_prob[b] = ninf;
+    fill_empty();
+    return;
+  }
+
+  // ------------------------------------------------------------------ loaders: chunk geometry
+  // Loader wave w takes rows w, w+4, ... of a chunk; its lanes stride across a row. Everything
+  // but the chunk's base is chunk-invariant, so the offsets are formed once: goff = byte offset
+  // from the chunk's first row (kVitNoUnit for a unit outside the geometry: its load is out of
+  // every range), loff = LDS element in the buffer (the junk behind it for such a unit).
+  const int NC = (S - 1 + R - 1) / R;  // chunks of transition rows 0..S-2
+  int goff[kVitUnits], loff[kVitUnits], goffo[OBS ? kVitUnits : 1], loffo[OBS ? kVitUnits : 1];
+  f32x4 lreg[kVitUnits];
+  float oreg[OBS ? kVitUnits : 1];
+  const bool loader = wave >= 1;
+  if (loader) {
+    const int w = wave - 1;
+    const int ppu = q.vec ? 2 : 1;                       // positions per log_trans unit
+    const int upr = (U + 64 * ppu - 1) / (64 * ppu);     // units per row and lane
+    const int upro = (U + 63) / 64;
+    vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+      constexpr int u = decltype(Ic)::value;
+      const int row = w + kVitLoaders * (u / upr);
+      const int p = (lane + 64 * (u % upr)) * ppu;
+      const bool ok = row < R && p < U;
+      goff[u] = ok ? (row * U + p) * 8 : kVitNoUnit;
+      loff[u] = ok ? row * kRow + (p % K) * kKs + p / K : R * kRow + lane;
+      if constexpr (OBS) {
+        const int rowo = w + kVitLoaders * (u / upro);
+        const int po = lane + 64 * (u % upro);
+        const bool oko = rowo < R && po < U;
+        goffo[u] = oko ? (rowo * U + po) * 4 : kVitNoUnit;
+        loffo[u] = oko ? rowo * kRow + (po % K) * kKs + po / K : R * kRow + lane;
+      }
+    });
+  }
+  // global -> registers: rows [c*R, min(c*R + R, S-1))
+  auto issue = [&](int c) __attribute__((always_inline)) {
+    const int r0 = c * R;
+    const int n = min(R, S - 1 - r0);
+    const __amdgpu_buffer_rsrc_t rs = brsrc(lt + (size_t)r0 * U * 2, (unsigned)(n * U) * 8u);
+    if (q.vec) {
+      vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+        constexpr int u = decltype(Ic)::value;
+        lreg[u] = rbuf_ld4(rs, goff[u], 0, 0);
+      });
+    } else {
+      vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+        constexpr int u = decltype(Ic)::value;
+        const f32x2 v = rbuf_ld2(rs, goff[u], 0, 0);
+        lreg[u].x = v.x; lreg[u].y = v.y;
+      });
+    }
+    if constexpr (OBS) {  // log_obs rows [c*R + 1, ...): the row a step adds is its own
+      const __amdgpu_buffer_rsrc_t ro = brsrc(lo + (size_t)(r0 + 1) * U, (unsigned)(n * U) * 4u);
+      vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+        constexpr int u = decltype(Ic)::value;
+        oreg[u] = rbuf_ld1(ro, goffo[u], 0, 0);
+      });
+    }
+  };
+  // registers -> LDS buffer c & 1 (rows past the chunk's end get zeros)
+  auto commit = [&](int c) __attribute__((always_inline)) {
+    float2* dst = ltb + (size_t)(c & 1) * bufsz;
+    if (q.vec) {
+      vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+        constexpr int u = decltype(Ic)::value;
+        dst[loff[u]] = make_float2(lreg[u].x, lreg[u].y);
+        dst[loff[u] + (K == 1 ? 1 : kKs)] = make_float2(lreg[u].z, lreg[u].w);
+      });
+    } else {
+      vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+        constexpr int u = decltype(Ic)::value;
+        dst[loff[u]] = make_float2(lreg[u].x, lreg[u].y);
+      });
+    }
+    if constexpr (OBS) {
+      float* dsto = obb + (size_t)(c & 1) * bufsz;
+      vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+        constexpr int u = decltype(Ic)::value;
+        dsto[loffo[u]] = oreg[u];
+      });
+    }
+  };
+
+  // ------------------------------------------------------------------ sweep
+  float V[K];
+  int mlo = 0, mhi = 0;  // lane k < K: the low / high half of this step's backpointer word k
+#pragma unroll
+  for (int k = 0; k < K; ++k) V[k] = ninf;
+  if (wave == 0 && lane == 0) V[0] = OBS ? lo[0] : 0.0f;
+  if (loader && NC > 0) {
+    issue(0);
+    commit(0);
+  }
+  __syncthreads();
+  for (int c = 0; c < NC; ++c) {
+    if (loader && c + 1 < NC) issue(c + 1);
+    if (wave == 0) {
+      const int r0 = c * R;
+      const int n = min(R, S - 1 - r0);
+      const float2* B = ltb + (size_t)(c & 1) * bufsz + lane;
+      const float* OB = obb + (size_t)(c & 1) * bufsz + lane;
+      struct Row {
+        float2 t[K];
+        float o[OBS ? K : 1];
+      };
+      auto ld = [&](Row& r, int i) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          r.t[k] = B[i * kRow + k * kKs];
+          if constexpr (OBS) r.o[k] = OB[i * kRow + k * kKs];
+        }
+      };
+      // V[s] from V[s-1] and transition row s-1
+      auto step = [&](const Row& r, int s) __attribute__((always_inline)) {
+        float mv[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) mv[k] = V[k] + r.t[k].y;  // V[s-1][p] + h[s-1][p]
+        const float left = shr1_ninf(mv[K - 1]);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const float stay = V[k] + r.t[k].x;
+          const float move = k == 0 ? left : mv[k > 0 ? k - 1 : 0];
+          const bool bp = move > stay;  // strict: a tie keeps the emit
+          float v = bp ? move : stay;
+          if constexpr (OBS) v = v + r.o[k];
+          V[k] = v;
+          if constexpr (MODE != 0) {
+            // the compare's SGPR pair goes straight into lane k (v_writelane: no select, no copy)
+            const unsigned long long w = __ballot(bp);
+            mlo = vit_writelane((int)(unsigned)w, k, mlo);
+            mhi = vit_writelane((int)(unsigned)(w >> 32), k, mhi);
+          }
+        }
+        const unsigned long long myw = ((unsigned long long)(unsigned)mhi << 32) | (unsigned)mlo;
+        if constexpr (MODE == 1) {
+          if (lane < K) bits[(size_t)s * K + lane] = myw;
+        } else if constexpr (MODE == 2) {
+          const int sr = s & (kVitStageRows - 1);
+          if (lane < K) stage[sr * K + lane] = myw;
+          if (sr == kVitStageRows - 1 || s == S - 1) {  // flush rows [s - sr, s]
+            unsigned long long* dst = ws + (size_t)(s - sr) * K;
+            for (int j = lane; j < (sr + 1) * K; j += 64) dst[j] = stage[j];
+          }
+        }
+      };
+      // two rows in registers: the next row's LDS reads go out before this row's arithmetic
+      Row ra, rb;
+      ld(ra, 0);
+      int i = 0;
+      for (; i + 1 < n; i += 2) {
+        ld(rb, i + 1);
+        step(ra, r0 + i + 1);
+        ld(ra, min(i + 2, n - 1));
+        step(rb, r0 + i + 2);
+      }
+      if (i < n) step(ra, r0 + i + 1);
+    }
+    if (loader && c + 1 < NC) commit(c + 1);
+    __syncthreads();
+  }
+
+  // ------------------------------------------------------------------ log_prob, feasibility
+  if (wave == 0) {
+    float v = ninf;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (K * lane + k == P - 1) v = V[k];
+    if (K * lane <= P - 1 && P - 1 < K * lane + K) {  // the one lane that holds P-1
+      if (a.flags & SSNT_FLAG_TERMINAL_EMIT) v = v + lt[((size_t)(S - 1) * U + (P - 1)) * 2];
+      a.log_prob[b] = v;
+      sh->feasible = v > ninf;
+      sh->s = S - 1;
+      sh->p = P - 1;
+    }
+    if constexpr (MODE == 2) __threadfence();  // the flushed words, before the other waves read them
+  }
+  if constexpr (MODE == 0) return;
+  __syncthreads();
+  if (!sh->feasible) {
+    fill_empty();
+    return;
+  }
+
+  // ------------------------------------------------------------------ backtrace by runs
+  for (int p = tid; p < P; p += kVitThreads) start[p] = 0;
+  if (tid == 0) start[P] = S;
+  for (;;) {
+    __syncthreads();
+    int s = sh->s, p = sh->p;
+    if (p <= 0 || s < 1) break;
+    int lo_row = 0;
+    const unsigned long long* wb = bits;
+    if constexpr (MODE == 2) {  // rows [lo_row, s] of the workspace -> LDS
+      lo_row = max(1, s - walk_rows + 1);
+      unsigned long long* src = ws + (size_t)lo_row * K;
+      const int nw = (s - lo_row + 1) * K;
+      for (int j0 = tid; j0 < nw; j0 += 8 * kVitThreads) {  // 8 loads in flight per lane
+        unsigned long long t[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          t[i] = __hip_atomic_load(src + min(j0 + i * kVitThreads, nw - 1), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          if (j0 + i * kVitThreads < nw) wbuf[j0 + i * kVitThreads] = t[i];
+      }
+      wb = wbuf;
+    }
+    const int first = max(lo_row, 1);
+    __syncthreads();
+    if (wave == 0) {
+      while (p > 0 && s >= first) {
+        const int ss = s - lane;
+        int bit = 0;
+        if (ss >= first) bit = (int)((wb[(size_t)(ss - lo_row) * K + (p & (K - 1))] >> (p / K)) & 1ull);
+        const unsigned long long m = __ballot(bit != 0);
+        if (m == 0) {
+          s = max(s - 64, first - 1);
+        } else {  // the nearest step below s that entered p
+          const int st = s - (__ffsll((long long)m) - 1);
+          if (lane == 0) start[p] = st;
+          s = st - 1;
+          p = p - 1;
+        }
+      }
+      if (lane == 0) {
+        sh->s = s;
+        sh->p = p;
+      }
+    }
+  }
+
+  // ------------------------------------------------------------------ outputs
+  if (dur_out)
+    for (int p = tid; p < U; p += kVitThreads) dur_out[p] = p < P ? start[p + 1] - start[p] : 0;
+  if (pos_out)
+    for (int s = tid; s < T; s += kVitThreads) {
+      int r = -1;
+      if (s < S) {  // the last p with start[p] <= s (start[0] = 0, increasing)
+        int lo_p = 0, hi_p = P - 1;
+        while (lo_p < hi_p) {
+          const int mid = (lo_p + hi_p + 1) >> 1;
+          if (start[mid] <= s) lo_p = mid; else hi_p = mid - 1;
+        }
+        r = lo_p;
+      }
+      pos_out[s] = r;
+    }
+}
+
+inline bool vit_aligned(const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & (m - 1)) == 0; }
+
+template <int K, bool OBS, int MODE>
+int launch_viterbi_k(const ViterbiArgs& a, const VitLayout& L, bool vec, hipStream_t st) {
+  VitParams q{};
+  q.R = L.R;
+  q.vec = vec;
+  q.start_off = (unsigned)L.start_off; q.lt_off = (unsigned)L.lt_off;
+  q.ob_off = (unsigned)L.ob_off; q.bits_off = (unsigned)L.bits_off;
+  auto kern = k_viterbi<K, OBS, MODE>;
+  if (L.total > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
+  hipLaunchKernelGGL(kern, dim3(a.B), dim3(kVitThreads), L.total, st, a, q);
+  return hipGetLastError() == hipSuccess ? SSNT_OK : SSNT_ERR_HIP;
+}
+
+template <int K, bool OBS>
+int launch_viterbi_mode(const ViterbiArgs& a, const VitLayout& L, bool vec, int mode, hipStream_t st) {
+  if (mode == 0) return launch_viterbi_k<K, OBS, 0>(a, L, vec, st);
+  if (mode == 1) return launch_viterbi_k<K, OBS, 1>(a, L, vec, st);
+  return launch_viterbi_k<K, OBS, 2>(a, L, vec, st);
+}
+
+template <bool OBS>
+int launch_viterbi_obs(const ViterbiArgs& a, const VitLayout& L, bool vec, int mode, hipStream_t st) {
+  switch (L.K) {
+    case 1: return launch_viterbi_mode<1, OBS>(a, L, vec, mode, st);
+    case 2: return launch_viterbi_mode<2, OBS>(a, L, vec, mode, st);
+    case 4: return launch_viterbi_mode<4, OBS>(a, L, vec, mode, st);
+    case 8: return launch_viterbi_mode<8, OBS>(a, L, vec, mode, st);
+    default: return launch_viterbi_mode<16, OBS>(a, L, vec, mode, st);
+  }
+}
+
+}  // namespace
+
+size_t viterbi_workspace_bytes(int B, int T, int U) {
+  if (vit_bits_fit(T, U)) return 0;
+  return (size_t)B * T * vit_k(U) * 8;
+}
+
+int launch_viterbi(const ViterbiArgs& a, hipStream_t st) {
+  if (a.B < 0 || a.T < 0 || a.U < 0 || (a.flags & ~SSNT_FLAG_TERMINAL_EMIT)) return SSNT_ERR_INVALID_ARG;
+  if (a.B == 0) return SSNT_OK;
+  if (!a.log_trans || !a.step_len || !a.pos_len || !a.log_prob) return SSNT_ERR_INVALID_ARG;
+  if (a.U > 1024) return SSNT_ERR_UNSUPPORTED;
+  if (!vit_aligned(a.log_trans, 8) || !vit_aligned(a.log_obs, 4)) return SSNT_ERR_UNSUPPORTED;
+  const bool path = a.position || a.duration;
+  const bool obs = a.log_obs != nullptr;
+  const int U = a.U > 0 ? a.U : 1;  // (T == 0 or U == 0: every utterance is infeasible)
+  const bool fit = a.T == 0 || a.U == 0 || vit_bits_fit(a.T, U);
+  if (path && !fit) {
+    const size_t need = viterbi_workspace_bytes(a.B, a.T, a.U);
+    if (!a.workspace || a.workspace_bytes < need || !vit_aligned(a.workspace, 8)) return SSNT_ERR_WORKSPACE;
+  }
+  const int mode = !path ? 0 : fit ? 1 : 2;
+  const bool vec = vit_aligned(a.log_trans, 16) && U % 2 == 0;
+  const VitLayout L = vit_pick(a.T, U, vec && !obs, obs, mode);
+  if (L.total > kLdsBudget) return SSNT_ERR_UNSUPPORTED;
+  return obs ? launch_viterbi_obs<true>(a, L, vec, mode, st) : launch_viterbi_obs<false>(a, L, vec, mode, st);
+}
+
+}  // namespace ssnt

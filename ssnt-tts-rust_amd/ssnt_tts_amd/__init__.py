@@ -5,7 +5,8 @@ The function names, argument order and meaning mirror the reference's Python op 
 130), over torch device tensors instead of TF graph tensors. Every call goes through the C ABI
 of ``lib/libssnt_tts_c.so`` (include/ssnt_tts_c.h) on torch's current HIP stream; there is no CPU
 fallback. Added beside them: the lattice forward-backward (``ssnt_fwd_bwd``,
-``SSNTLatticeLoss``) and a fused multi-step decode (``lattice_beam_search_decode``).
+``SSNTLatticeLoss``), the exact best path over the same lattice (``ssnt_viterbi_align``) and a
+fused multi-step decode (``lattice_beam_search_decode``).
 
 Errors the reference raises by panicking (v2 "no candidate", upsample duration mismatch,
 out-of-range branch) are raised here as ``SsntError`` when ``check=True`` (the default), which
@@ -25,7 +26,8 @@ FLAG_ZERO_INFINITY = 2
 __all__ = [
     "beam_search_decode", "extract_best_beam_branch", "ssnt_tts_v2_beam_search_decode",
     "order_beam_branch", "upsample_source_indexes", "tone_latent_beam_search_decode",
-    "levenshtein_edit_distance", "ssnt_fwd_bwd", "SSNTLatticeLoss", "ssnt_lattice_loss",
+    "levenshtein_edit_distance", "ssnt_fwd_bwd", "ssnt_viterbi_align", "SSNTLatticeLoss",
+    "ssnt_lattice_loss",
     "lattice_beam_search_decode", "v2_lattice_beam_search_decode",
     "tone_latent_lattice_beam_search_decode", "v2_fwd_bwd", "V2DurationLoss", "v2_duration_loss",
     "SsntError", "FLAG_TERMINAL_EMIT", "FLAG_ZERO_INFINITY",
@@ -376,6 +378,58 @@ def _fwd_bwd_debug64(log_trans, step_len, pos_len, log_obs, terminal_emit, zero_
         res["grad"] = grad
     if gobs is not None:
         res["grad_obs"] = gobs
+    return res
+
+
+def ssnt_viterbi_align(log_trans, step_len, pos_len, log_obs=None, *, terminal_emit=True,
+                       need_path=True, check=False, out=None):
+    """Exact best path (Viterbi) over the emit/shift lattice.
+
+    Inputs as ``ssnt_fwd_bwd``. Returns a dict with ``log_prob`` (B,) f32, the log-probability
+    of the most probable monotone alignment; ``position`` (B,T) i32, the input position of every
+    step on it (-1 for steps >= S_b); ``duration`` (B,U) i32, the steps each position holds (0
+    for positions >= P_b); ``status``. An infeasible utterance gets -inf, -1 and 0. A tie keeps
+    the emit. ``need_path=False`` computes ``log_prob`` only. ``out`` may pass preallocated
+    tensors under the same keys."""
+    lib = load(require_gpu=True)
+    lt = _dev(log_trans, torch.float32, "log_trans")
+    dev = lt.device
+    B, T, U, two = lt.shape
+    if two != 2:
+        raise ValueError("log_trans must be (B,T,U,2)")
+    sl = _dev(step_len, torch.int32, "step_len").reshape(B)
+    pl = _dev(pos_len, torch.int32, "pos_len").reshape(B)
+    lo = None if log_obs is None else _dev(log_obs, torch.float32, "log_obs").reshape(B, T, U)
+    flags = FLAG_TERMINAL_EMIT if terminal_emit else 0
+    out = dict(out or {})
+
+    def _buf(key, shape, dtype, want):
+        if not want:
+            return None
+        t = out.get(key)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        elif tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"out[{key!r}] must be a contiguous {dtype} tensor of shape {shape}")
+        return t
+
+    lp = _buf("log_prob", (B,), torch.float32, True)
+    pos = _buf("position", (B, T), torch.int32, need_path)
+    dur = _buf("duration", (B, U), torch.int32, need_path)
+    wsb = int(lib.ssnt_viterbi_align_workspace_size(B, T, U)) if need_path else 0
+    ws = _workspace(dev, wsb)
+    st = out.get("status")
+    if st is None:
+        st = _status(dev)
+    else:
+        st.zero_()
+    rc = lib.ssnt_viterbi_align_device(_p(lt), _p(lo), _p(sl), _p(pl), B, T, U, flags, _p(lp),
+                                       _p(pos), _p(dur), _p(ws), wsb, _p(st), _stream(dev))
+    _finish("ssnt_viterbi_align", rc, st, check)
+    res = {"log_prob": lp, "status": st}
+    if need_path:
+        res["position"] = pos
+        res["duration"] = dur
     return res
 
 
