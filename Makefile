@@ -28,8 +28,7 @@ lib: $(LIB)
 oracle: $(ORACLE)
 
 # A/B build (tests and tools only; include/ssnt_tts_c_ab.h): the product plus process-wide kernel
-# / staging / sync knobs and the selection decode ordering. Own soname, so a
-# process can load it beside the product library.
+# / staging / sync knobs. Own soname, so a process can load it beside the product library.
 ABDIR     := $(LIBDIR)/ab
 AB_OBJS   := $(patsubst $(CSRC)/%.hip,$(ABDIR)/obj/%.o,$(AB_SRCS))
 lib-ab: $(ABDIR)/libssnt_tts_c_ab.so

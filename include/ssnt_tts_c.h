@@ -128,7 +128,7 @@ int ssnt_version(char *buf, size_t len);
  * chosen from the shape and alignment alone (no process-wide state). */
 size_t ssnt_fwd_bwd_workspace_size(int batch, int max_steps, int max_pos);
 /* Name of the forward-backward kernel instance the calling thread's last ssnt_fwd_bwd* call
- * dispatched (e.g. "k_fwd_bwd_stream<K=2,OBS=0,LDS=1,NC=3,NH=4,RS=0,NV=0>"; launches of one call
+ * dispatched (e.g. "k_fwd_bwd_stream<K=2,OBS=0,LDS=1,NC=3,NH=4,NV=0>"; launches of one call
  * joined by '+'), copied into buf (truncated to len); returns its full length. Lets a profile be
  * matched to the kernel a benchmark actually ran. */
 int ssnt_fwd_bwd_last_kernel(char *buf, size_t len);

@@ -25,19 +25,12 @@ extern "C" {
 /* forward-backward kernel: 0 default dispatch, 1 two-wave kernel, 2 segmented kernel at every U
  * it takes; env SSNT_FWD_BWD_KERNEL=simple selects 1 at first use */
 int ssnt_fwd_bwd_set_variant(int variant);
-/* segmented kernel: positions per lane (1 or 2) and the workgroup split (-1 auto, 0, 1; 2: phase 2
- * only, a study form) */
+/* segmented kernel: positions per lane (1 or 2) and the workgroup split (-1 auto, 0, 1) */
 int ssnt_fwd_bwd_wide_lanes(int k);
 int ssnt_fwd_bwd_wide_split(int mode);
 /* segmented kernel, split form: the downstream workgroup's first compute wave sleeps `sleeps`
  * x s_sleep 127 per block (0 default), so the receiver runs a whole ring ahead (race test) */
 int ssnt_fwd_bwd_wide_lag(int sleeps);
-/* streaming kernel: 0 default rings; 16 / 32 converter ring slots with the rows in the workspace */
-int ssnt_fwd_bwd_stream_ring(int r);
-/* fused decodes: -1 default, 0 full rank, 1 selection ordering */
-int ssnt_fused_decode_select(int mode);
-/* tone fused decode: waves its 20-candidate rank is split over (1, 2, 4; -1 the product's choice) */
-int ssnt_fused_decode_tone_waves(int n);
 /* per-step reference symbols: host staging 0 copies / 1 zero-copy; completion 0 stream
  * synchronise / 1 hipStreamWriteValue32 word / 2 flag kernel; both return the previous mode */
 int ssnt_set_host_staging(int mode);

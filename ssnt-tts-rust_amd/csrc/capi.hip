@@ -390,6 +390,44 @@ __global__ void k_null() {}
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// the launch arguments of a forward-backward call (the loss sum and raw-state fields stay null)
+FwdBwdArgs fwd_bwd_args(const float* log_trans, const float* log_obs, const int* step_len,
+                        const int* pos_len, int batch, int max_steps, int max_pos, int flags,
+                        float* loss, float* grad_trans, float* grad_obs, float* log_alpha,
+                        float* log_beta, void* workspace, size_t workspace_bytes, int* status) {
+  FwdBwdArgs a{};
+  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
+  a.B = batch; a.T = max_steps; a.U = max_pos; a.flags = flags;
+  a.loss = loss; a.grad = grad_trans; a.grad_obs = grad_obs;
+  a.log_alpha = log_alpha; a.log_beta = log_beta;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  return a;
+}
+
+// the launch arguments of one decode step: what every variant takes (v1 and tone: all but
+// scalar_input_length / special_id), and v2's additions
+StepArgs step_args(Variant variant, int batch_size, int beam_width, int classes, const float* h,
+                   const float* log_prob_history, const bool* is_finished, const int* t,
+                   const int* u, const int* input_length, int* prediction, float* log_probs,
+                   int* next_t, int* next_u, bool* next_is_finished, int* beam_branch, int* status) {
+  StepArgs a{};
+  a.variant = variant;
+  a.B = batch_size; a.W = beam_width; a.Wmax = beam_width; a.C = classes;
+  a.h = h; a.hist = log_prob_history; a.fin = is_finished; a.t = t; a.u = u;
+  a.input_length = input_length;
+  a.prediction = prediction; a.log_prob = log_probs; a.next_t = next_t; a.next_u = next_u;
+  a.next_fin = next_is_finished; a.beam_branch = beam_branch; a.status = status;
+  return a;
+}
+StepArgs v2_step_args(StepArgs a, const int* total_duration, const int* duration_table,
+                      const int* output_length, int zero_duration_id, bool allow_skip,
+                      bool test_mode, int* next_total_duration) {
+  a.total = total_duration; a.table = duration_table; a.output_length = output_length;
+  a.special_id = zero_duration_id; a.allow_skip = allow_skip; a.test_mode = test_mode;
+  a.next_total = next_total_duration;
+  return a;
+}
+
 }  // namespace
 }  // namespace ssnt
 
@@ -446,15 +484,11 @@ void ssnt_tts_beam_search_decode(const float* h, const float* log_prob_history,
             ot = p.add_out(next_t, W * 4), ou = p.add_out(next_u, W * 4),
             of = p.add_out(next_is_finished, W), ob = p.add_out(beam_branch, W * 4);
   stage_in(p, fn, true);
-  StepArgs a{};
-  a.variant = Variant::V1;
-  a.B = 1; a.W = beam_width; a.Wmax = beam_width; a.C = 2;
-  a.h = p.din<float>(ih); a.hist = p.din<float>(ihist); a.fin = p.din<bool>(ifin);
-  a.t = p.din<int>(it); a.u = p.din<int>(iu);
-  a.input_length = nullptr; a.scalar_input_length = max_t;
-  a.prediction = p.dout<int>(op); a.log_prob = p.dout<float>(ol); a.next_t = p.dout<int>(ot);
-  a.next_u = p.dout<int>(ou); a.next_fin = p.dout<bool>(of); a.beam_branch = p.dout<int>(ob);
-  a.status = p.dstatus();
+  StepArgs a = step_args(Variant::V1, 1, beam_width, 2, p.din<float>(ih), p.din<float>(ihist),
+                         p.din<bool>(ifin), p.din<int>(it), p.din<int>(iu), nullptr, p.dout<int>(op),
+                         p.dout<float>(ol), p.dout<int>(ot), p.dout<int>(ou), p.dout<bool>(of),
+                         p.dout<int>(ob), p.dstatus());
+  a.scalar_input_length = max_t;
   stage_out(p, launch_decode_step(a, g_ctx.stream), fn, true);
 }
 
@@ -516,18 +550,13 @@ void ssnt_tts_v2_beam_search_decode(const float* h, const float* log_prob_histor
             of = p.add_out(next_is_finished, BW), otd = p.add_out(next_total_duration, BW * 4),
             ob = p.add_out(beam_branch, BW * 4);
   stage_in(p, fn, true);
-  StepArgs a{};
-  a.variant = Variant::V2;
-  a.B = batch_size; a.W = beam_width; a.Wmax = beam_width; a.C = duration_class_size;
-  a.h = p.din<float>(ih); a.hist = p.din<float>(ihist); a.fin = p.din<bool>(ifin);
-  a.total = p.din<int>(itot); a.table = p.din<int>(itab);
-  a.t = p.din<int>(it); a.u = p.din<int>(iu);
-  a.input_length = p.din<int>(iil); a.output_length = p.din<int>(iol);
-  a.special_id = zero_duration_id; a.allow_skip = allow_skip; a.test_mode = test_mode;
-  a.prediction = p.dout<int>(op); a.log_prob = p.dout<float>(ol); a.next_t = p.dout<int>(ot);
-  a.next_u = p.dout<int>(ou); a.next_fin = p.dout<bool>(of); a.next_total = p.dout<int>(otd);
-  a.beam_branch = p.dout<int>(ob);
-  a.status = p.dstatus();
+  const StepArgs a = v2_step_args(
+      step_args(Variant::V2, batch_size, beam_width, duration_class_size, p.din<float>(ih),
+                p.din<float>(ihist), p.din<bool>(ifin), p.din<int>(it), p.din<int>(iu),
+                p.din<int>(iil), p.dout<int>(op), p.dout<float>(ol), p.dout<int>(ot),
+                p.dout<int>(ou), p.dout<bool>(of), p.dout<int>(ob), p.dstatus()),
+      p.din<int>(itot), p.din<int>(itab), p.din<int>(iol), zero_duration_id, allow_skip, test_mode,
+      p.dout<int>(otd));
   stage_out(p, launch_decode_step(a, g_ctx.stream), fn, true);
 }
 
@@ -599,15 +628,11 @@ void tone_latent_beam_search_decode(const float* h, const float* log_prob_histor
             ot = p.add_out(next_t, BW * 4), ou = p.add_out(next_u, BW * 4),
             of = p.add_out(next_is_finished, BW), ob = p.add_out(beam_branch, BW * 4);
   stage_in(p, fn, true);
-  StepArgs a{};
-  a.variant = Variant::Tone;
-  a.B = batch_size; a.W = beam_width; a.Wmax = beam_width; a.C = tone_class_size;
-  a.h = p.din<float>(ih); a.hist = p.din<float>(ihist); a.fin = p.din<bool>(ifin);
-  a.t = p.din<int>(it); a.u = p.din<int>(iu); a.input_length = p.din<int>(iil);
+  StepArgs a = step_args(Variant::Tone, batch_size, beam_width, tone_class_size, p.din<float>(ih),
+                         p.din<float>(ihist), p.din<bool>(ifin), p.din<int>(it), p.din<int>(iu),
+                         p.din<int>(iil), p.dout<int>(op), p.dout<float>(ol), p.dout<int>(ot),
+                         p.dout<int>(ou), p.dout<bool>(of), p.dout<int>(ob), p.dstatus());
   a.special_id = empty_tone_id;
-  a.prediction = p.dout<int>(op); a.log_prob = p.dout<float>(ol); a.next_t = p.dout<int>(ot);
-  a.next_u = p.dout<int>(ou); a.next_fin = p.dout<bool>(of); a.beam_branch = p.dout<int>(ob);
-  a.status = p.dstatus();
   stage_out(p, launch_decode_step(a, g_ctx.stream), fn, true);
 }
 
@@ -668,11 +693,6 @@ int ssnt_set_host_sync(int mode) {
   return g_sync_mode.exchange(mode);
 }
 
-// the fused decodes' step ordering: -1 default, 0 full rank, 1 selection
-int ssnt_fused_decode_select(int mode) { return set_fused_decode_select(mode); }
-// waves of the tone fused decode's rank (1, 2, 4; -1 the product's choice)
-int ssnt_fused_decode_tone_waves(int n) { return set_fused_decode_tone_waves(n); }
-
 // the long-row kernel's lane width
 int ssnt_fwd_bwd_wide_lanes(int k) { return set_fwd_bwd_wide_lanes(k); }
 // the long-row kernel's workgroup split (-1 auto, 0 one workgroup per direction, 1 two
@@ -681,8 +701,6 @@ int ssnt_fwd_bwd_wide_split(int mode) { return set_fwd_bwd_wide_split(mode); }
 // the split form's downstream first compute wave idles `sleeps` x s_sleep 127 per block, so the
 // receiver proxy runs a whole ring ahead of it (tests/test_gpu_fwd_bwd.py hand-off race test)
 int ssnt_fwd_bwd_wide_lag(int sleeps) { return set_fwd_bwd_wide_lag(sleeps); }
-// the streaming kernel's ring depth (16 / 32 slots, rows in the workspace; 0 default)
-int ssnt_fwd_bwd_stream_ring(int r) { return set_stream_ring(r); }
 
 // Per-step symbol latency breakdown (tools/bench_step_symbols.py).
 // enable = 1 resets and starts the calling thread's phase clock; 0 stops it and writes the mean
@@ -735,12 +753,9 @@ int ssnt_fwd_bwd_device(const float* log_trans, const float* log_obs, const int*
                         float* loss, float* grad_trans, float* grad_obs, float* log_alpha,
                         float* log_beta, void* workspace, size_t workspace_bytes, int* status,
                         void* stream) {
-  FwdBwdArgs a{};
-  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
-  a.B = batch; a.T = max_steps; a.U = max_pos; a.flags = flags;
-  a.loss = loss; a.grad = grad_trans; a.grad_obs = grad_obs;
-  a.log_alpha = log_alpha; a.log_beta = log_beta;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  const FwdBwdArgs a = fwd_bwd_args(log_trans, log_obs, step_len, pos_len, batch, max_steps, max_pos,
+                                    flags, loss, grad_trans, grad_obs, log_alpha, log_beta,
+                                    workspace, workspace_bytes, status);
   return launch_fwd_bwd(a, as_stream(stream));
 }
 
@@ -754,11 +769,10 @@ int ssnt_fwd_bwd_debug64_device(const float* log_trans, const float* log_obs, co
                                 int flags, double* loss, float* grad_trans, float* grad_obs,
                                 double* log_alpha, double* log_beta, void* workspace,
                                 size_t workspace_bytes, int* status, void* stream) {
-  FwdBwdArgs a{};
-  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
-  a.B = batch; a.T = max_steps; a.U = max_pos; a.flags = flags;
-  a.grad = grad_trans; a.grad_obs = grad_obs;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  // (loss and the debug rows: the float64 arrays go to the launcher beside the arguments)
+  const FwdBwdArgs a = fwd_bwd_args(log_trans, log_obs, step_len, pos_len, batch, max_steps, max_pos,
+                                    flags, nullptr, grad_trans, grad_obs, nullptr, nullptr,
+                                    workspace, workspace_bytes, status);
   if (!log_trans || !step_len || !pos_len) return SSNT_ERR_INVALID_ARG;
   if (grad_obs && !log_obs) return SSNT_ERR_INVALID_ARG;
   return launch_fwd_bwd_debug64(a, loss, log_alpha, log_beta, as_stream(stream));
@@ -770,12 +784,9 @@ int ssnt_fwd_bwd_sum_device(const float* log_trans, const float* log_obs, const 
                             float* log_beta, void* workspace, size_t workspace_bytes, int* status,
                             float* loss_sum, void* sum_state, void* stream) {
   if (!loss_sum) return SSNT_ERR_INVALID_ARG;
-  FwdBwdArgs a{};
-  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
-  a.B = batch; a.T = max_steps; a.U = max_pos; a.flags = flags;
-  a.loss = loss; a.grad = grad_trans; a.grad_obs = grad_obs;
-  a.log_alpha = log_alpha; a.log_beta = log_beta;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  FwdBwdArgs a = fwd_bwd_args(log_trans, log_obs, step_len, pos_len, batch, max_steps, max_pos, flags,
+                              loss, grad_trans, grad_obs, log_alpha, log_beta, workspace,
+                              workspace_bytes, status);
   a.loss_sum = loss_sum; a.sum_state = sum_state;
   return launch_fwd_bwd(a, as_stream(stream));
 }
@@ -845,18 +856,11 @@ int ssnt_fwd_bwd(const float* log_trans, const float* log_obs, const int* step_l
   rc = direct ? stage_in_direct(p, fn, ws) : stage_in(p, fn, false, ws, false);
   if (rc != SSNT_OK) return rc;
   const size_t ws_off = Plan::align(p.total);
-  FwdBwdArgs a{};
-  a.log_trans = p.din<float>(ilt); a.log_obs = log_obs ? p.din<float>(ilo) : nullptr;
-  a.step_len = p.din<int>(isl); a.pos_len = p.din<int>(ipl);
-  a.B = batch; a.T = max_steps; a.U = max_pos; a.flags = flags;
-  a.loss = p.dout<float>(ol);
-  a.grad = og >= 0 ? p.dout<float>(og) : nullptr;
-  a.grad_obs = ogo >= 0 ? p.dout<float>(ogo) : nullptr;
-  a.log_alpha = ola >= 0 ? p.dout<float>(ola) : nullptr;
-  a.log_beta = olb >= 0 ? p.dout<float>(olb) : nullptr;
-  a.workspace = ws ? g_ctx.d + ws_off : nullptr;
-  a.workspace_bytes = ws;
-  a.status = p.dstatus();
+  auto out = [&](int i) { return i >= 0 ? p.dout<float>(i) : nullptr; };
+  const FwdBwdArgs a = fwd_bwd_args(p.din<float>(ilt), log_obs ? p.din<float>(ilo) : nullptr,
+                                    p.din<int>(isl), p.din<int>(ipl), batch, max_steps, max_pos, flags,
+                                    p.dout<float>(ol), out(og), out(ogo), out(ola), out(olb),
+                                    ws ? g_ctx.d + ws_off : nullptr, ws, p.dstatus());
   if (direct) return stage_out_direct(p, launch_fwd_bwd(a, g_ctx.stream));
   return stage_out(p, launch_fwd_bwd(a, g_ctx.stream), fn, false);
 }
@@ -870,13 +874,9 @@ int ssnt_beam_search_decode_device(const float* h, const float* log_prob_history
   if (!h || !log_prob_history || !is_finished || !t || !u || !input_length || !prediction ||
       !log_probs || !next_t || !next_u || !next_is_finished || !beam_branch)
     return SSNT_ERR_INVALID_ARG;
-  StepArgs a{};
-  a.variant = Variant::V1;
-  a.B = batch_size; a.W = beam_width; a.Wmax = beam_width; a.C = 2;
-  a.h = h; a.hist = log_prob_history; a.fin = is_finished; a.t = t; a.u = u;
-  a.input_length = input_length;
-  a.prediction = prediction; a.log_prob = log_probs; a.next_t = next_t; a.next_u = next_u;
-  a.next_fin = next_is_finished; a.beam_branch = beam_branch; a.status = status;
+  const StepArgs a = step_args(Variant::V1, batch_size, beam_width, 2, h, log_prob_history, is_finished,
+                               t, u, input_length, prediction, log_probs, next_t, next_u,
+                               next_is_finished, beam_branch, status);
   return launch_decode_step(a, as_stream(stream));
 }
 
@@ -894,16 +894,12 @@ int ssnt_v2_beam_search_decode_device(const float* h, const float* log_prob_hist
       !input_length || !output_length || !prediction || !log_probs || !next_t || !next_u ||
       !next_is_finished || !next_total_duration || !beam_branch)
     return SSNT_ERR_INVALID_ARG;
-  StepArgs a{};
-  a.variant = Variant::V2;
-  a.B = batch_size; a.W = beam_width; a.Wmax = beam_width; a.C = duration_class_size;
-  a.h = h; a.hist = log_prob_history; a.fin = is_finished; a.total = total_duration;
-  a.table = duration_table; a.t = t; a.u = u;
-  a.input_length = input_length; a.output_length = output_length;
-  a.special_id = zero_duration_id; a.allow_skip = allow_skip; a.test_mode = test_mode;
-  a.prediction = prediction; a.log_prob = log_probs; a.next_t = next_t; a.next_u = next_u;
-  a.next_fin = next_is_finished; a.next_total = next_total_duration;
-  a.beam_branch = beam_branch; a.status = status;
+  const StepArgs a = v2_step_args(
+      step_args(Variant::V2, batch_size, beam_width, duration_class_size, h, log_prob_history,
+                is_finished, t, u, input_length, prediction, log_probs, next_t, next_u,
+                next_is_finished, beam_branch, status),
+      total_duration, duration_table, output_length, zero_duration_id, allow_skip, test_mode,
+      next_total_duration);
   return launch_decode_step(a, as_stream(stream));
 }
 
@@ -918,13 +914,10 @@ int ssnt_tone_latent_beam_search_decode_device(const float* h, const float* log_
   if (!h || !log_prob_history || !is_finished || !t || !u || !input_length || !prediction ||
       !log_probs || !next_t || !next_u || !next_is_finished || !beam_branch)
     return SSNT_ERR_INVALID_ARG;
-  StepArgs a{};
-  a.variant = Variant::Tone;
-  a.B = batch_size; a.W = beam_width; a.Wmax = beam_width; a.C = tone_class_size;
-  a.h = h; a.hist = log_prob_history; a.fin = is_finished; a.t = t; a.u = u;
-  a.input_length = input_length; a.special_id = empty_tone_id;
-  a.prediction = prediction; a.log_prob = log_probs; a.next_t = next_t; a.next_u = next_u;
-  a.next_fin = next_is_finished; a.beam_branch = beam_branch; a.status = status;
+  StepArgs a = step_args(Variant::Tone, batch_size, beam_width, tone_class_size, h, log_prob_history,
+                         is_finished, t, u, input_length, prediction, log_probs, next_t, next_u,
+                         next_is_finished, beam_branch, status);
+  a.special_id = empty_tone_id;
   return launch_decode_step(a, as_stream(stream));
 }
 

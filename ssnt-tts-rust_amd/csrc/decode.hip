@@ -11,6 +11,7 @@
 #include <atomic>
 
 #include "decode_dev.h"
+#include "launch_util.h"
 
 namespace ssnt {
 namespace {
@@ -192,8 +193,6 @@ __global__ __launch_bounds__(64) void k_levenshtein(int B, int L, const int* __r
   if (lane == 0) dist[i] = e[N];
 }
 
-inline int last_error() { return hipGetLastError() == hipSuccess ? SSNT_OK : SSNT_ERR_HIP; }
-
 }  // namespace
 
 int launch_decode_step(const StepArgs& a, hipStream_t st) {
@@ -217,7 +216,7 @@ int launch_decode_step(const StepArgs& a, hipStream_t st) {
     }
   }
   hipLaunchKernelGGL(k_decode_step, dim3(a.B), dim3(64), lds, st, a);
-  return last_error();
+  return launch_status();
 }
 
 int launch_extract_best(int B, int W, int U, const int* best_final_branch, const int* beam_branch,
@@ -229,7 +228,7 @@ int launch_extract_best(int B, int W, int U, const int* best_final_branch, const
   const size_t lds = (size_t)chunk * W * 2 * sizeof(int);
   hipLaunchKernelGGL(k_backtrace, dim3(B), dim3(64), lds, st, B, W, U, 1, best_final_branch,
                      beam_branch, t_history, best_beam_branch, best_t_history, chunk, status);
-  return last_error();
+  return launch_status();
 }
 
 int launch_order_beam_branch(int B, int W, int T, const int* final_branch, const int* beam_branch,
@@ -241,7 +240,7 @@ int launch_order_beam_branch(int B, int W, int T, const int* final_branch, const
   const size_t lds = (size_t)chunk * W * 2 * sizeof(int);
   hipLaunchKernelGGL(k_backtrace, dim3(B), dim3(64), lds, st, B, W, T, W, final_branch,
                      beam_branch, nullptr, ordered, nullptr, chunk, status);
-  return last_error();
+  return launch_status();
 }
 
 int launch_upsample(int B, int W, int T, int max_u, const int* duration, const int* output_length,
@@ -252,7 +251,7 @@ int launch_upsample(int B, int W, int T, int max_u, const int* duration, const i
   if (lds > 150 * 1024) return SSNT_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(k_upsample, dim3(B * W), dim3(64), lds, st, B * W, T, max_u, duration,
                      output_length, out, status);
-  return last_error();
+  return launch_status();
 }
 
 int launch_levenshtein(int B, int max_length, const int* a, const int* b, const int* a_len,
@@ -263,7 +262,7 @@ int launch_levenshtein(int B, int max_length, const int* a, const int* b, const 
   if (lds > 150 * 1024) return SSNT_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(k_levenshtein, dim3(B), dim3(64), lds, st, B, max_length, a, b, a_len,
                      b_len, dist);
-  return last_error();
+  return launch_status();
 }
 
 }  // namespace ssnt

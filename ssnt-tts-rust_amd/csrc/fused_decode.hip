@@ -23,11 +23,11 @@
 // beam has u == s, so its row is lattice[b,s]); rows are prefetched kAhead steps ahead.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <type_traits>
 
 #include "buffer_ops.h"
 #include "decode_dev.h"
+#include "launch_util.h"
 
 namespace ssnt {
 namespace {
@@ -56,10 +56,6 @@ __device__ unsigned long long g_dec_diag[8];
   } while (0)
 #endif
 
-// buffer resource over [base, base + bytes): loads past the end return 0
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t brsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
 constexpr int kV1Regs = 4;   // v1 lattice row floats per lane: the row is staged while 2U <= 256
 constexpr int kChunk = 32;   // per-step outputs staged in LDS and flushed every kChunk steps
 constexpr int kRec = 4;      // ints per staged output record (one per step and slot)
@@ -111,12 +107,9 @@ __device__ __forceinline__ void lds_order() { asm volatile("" ::: "memory"); }
 // (each compares every candidate with 16 of the keys; the partial counts cross through LDS, one
 // barrier per step), everything else runs identically in each wave, and wave 0 alone writes
 // outputs. The 64 compares of one wave were a third of the step.
-// Tone's 20 candidates (NMAX 32: two in-wave replicas) can split their rank over TW waves the
-// same way (each wave counts JN / TW of its replica's keys): TW is a template parameter, chosen by
-// the launcher (kToneWaves; the A/B build's ssnt_fused_decode_tone_waves overrides it).
-constexpr int fused_waves(Variant v, int nmax, bool sel, int tw = 1) {
-  return (nmax == 64 && v != Variant::V1 && !sel) ? 4 : (nmax == 32 && v == Variant::Tone && !sel) ? tw : 1;
-}
+// Tone's 20 candidates (NMAX 32: two in-wave replicas) rank on one wave: the rank split over 2 / 4
+// waves (TW) measured 202 / 215 us against 189 us at configs[4]; retired to git history.
+constexpr int fused_waves(Variant v, int nmax) { return (nmax == 64 && v != Variant::V1) ? 4 : 1; }
 
 struct RegLayout {
   size_t ring, hist, row, total;
@@ -138,18 +131,16 @@ struct RegLayout {
 
 // NMAX: a compile-time bound on n (8, 16, 32 or 64): the rank loop is unrolled to NMAX so its
 // broadcast key reads are issued back to back instead of one LDS round trip per pair.
-// SEL: the step's ordering by selection instead of a full rank (select_step below); the two
-// forms give identical outputs.
 // One wave per workgroup and (staged rows, history) LDS enough that one workgroup fills a CU: the
 // compiler is told one wave per SIMD, so it may spend registers on keeping loads in flight (its
 // default occupancy target of 8 waves caps a wave at 64 VGPRs, which serialised the rank's
 // broadcast key reads into one LDS round trip per two keys).
-template <Variant V, bool STAGED, int NMAX, bool WHOLE, bool SEL, int TW = 1>
-__global__ __launch_bounds__(64 * fused_waves(V, NMAX, SEL, TW)) __attribute__((amdgpu_waves_per_eu(1, 1)))
+template <Variant V, bool STAGED, int NMAX, bool WHOLE>
+__global__ __launch_bounds__(64 * fused_waves(V, NMAX)) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_fused_reg(FusedDecodeArgs a, int hist_lds) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr bool kV1 = V == Variant::V1, kV2 = V == Variant::V2;
-  constexpr int kNW = fused_waves(V, NMAX, SEL, TW);
+  constexpr int kNW = fused_waves(V, NMAX);
   // sort and compaction through LDS records (v2 / tone beyond 16 candidates, staged v1); the
   // other forms permute the fields across lanes
   constexpr bool kRecs = (NMAX > 16 && !kV1) || (kV1 && STAGED);
@@ -389,86 +380,6 @@ void k_fused_reg(FusedDecodeArgs a, int hist_lds) {
     }
     int g_lp, g_ntu, g_pk, g_tot;
     DSTAMP(0);
-    if constexpr (SEL) {
-      // ---- selection (src/lib.rs:161-168, src/v2.rs:280-308): only the first W kept candidates
-      // of the sorted, deduplicated list (and the v2 diagonal one) are ever used, so they are
-      // extracted one by one instead of ranking all n. A round takes the largest key among the
-      // candidates not yet extracted (group max, ties to the lowest generation index: the stable
-      // descending order), reads its fields into scalars and keeps it unless it equals the
-      // previous extracted candidate (consecutive dedup: equal to the previous extracted is equal
-      // to the last kept, eq_ignore_parent being an equivalence). Kept record k goes to lane k.
-      const unsigned key = valid ? lp_key(lp) : 0u;  // valid keys are >= 1
-      const int lpb = __float_as_int(lp);
-      const int pk = code | (fin << 7) | (w << 8);
-      const int ntu = (nt << 16) | (nu & 0xffff);
-      const int v0b = __float_as_int(nv0), v1b = __float_as_int(nv1);
-      u64 rem = ballot(valid != 0) & kGrp;  // (replicas mirror replica 0)
-      int nk = 0;
-      int r_lp = 0, r_ntu = 0, r_pk = 0, r_tot = 0, r_v0 = 0, r_v1 = 0;
-      int q_lp = 0, q_ntu = 0, q_pk = 0, q_tot = 0;
-      bool have_q = false;
-      while (rem != 0 && nk < W) {
-        const bool in = ((rem >> c) & 1ull) != 0;
-        const unsigned m = group_max_u32<NMAX>(in ? key : 0u);
-        const int sel = (int)__builtin_ctzll(ballot(in && key == m) & kGrp);
-        rem &= ~(1ull << sel);
-        const int f_lp = readlane_i(lpb, sel), f_ntu = readlane_i(ntu, sel), f_pk = readlane_i(pk, sel);
-        const int f_tot = kV2 ? readlane_i(tot, sel) : 0;
-        const bool dup = have_q && ((f_pk ^ q_pk) & 0xff) == 0 &&
-                         __int_as_float(f_lp) == __int_as_float(q_lp) && f_ntu == q_ntu && f_tot == q_tot;
-        if (!dup) {
-          const bool mine = lane == nk;
-          r_lp = mine ? f_lp : r_lp;
-          r_ntu = mine ? f_ntu : r_ntu;
-          r_pk = mine ? f_pk : r_pk;
-          if constexpr (kV2) r_tot = mine ? f_tot : r_tot;
-          if constexpr (kV1 && STAGED) {
-            r_v0 = mine ? readlane_i(v0b, sel) : r_v0;
-            r_v1 = mine ? readlane_i(v1b, sel) : r_v1;
-          }
-          ++nk;
-        }
-        q_lp = f_lp; q_ntu = f_ntu; q_pk = f_pk; q_tot = f_tot;
-        have_q = true;
-      }
-      if constexpr (kV2) {  // assert_ne!(n_results, 0) (src/v2.rs:292); v1/tone always keep one
-        if (nk == 0) return false;
-      }
-      // v2 diagonal candidate (src/v2.rs:283-289): the first kept one on the diagonal is the
-      // largest-key valid one on it -- a dedup-dropped candidate equals its kept predecessor in
-      // total and next_t, so that predecessor is on the diagonal too and comes first
-      bool have_d = false;
-      int d_lp = 0, d_ntu = 0, d_pk = 0, d_tot = 0;
-      if constexpr (kV2) {
-        if (!a.test_mode) {
-          const float diff = (float)tot - o_over_i * (float)(u64)(unsigned)nt;
-          const bool on = valid && diff >= -20.0f && diff <= 0.0f;
-          const u64 dm = ballot(on) & kGrp;
-          if (dm) {
-            const unsigned m = group_max_u32<NMAX>(on ? key : 0u);
-            const int ds = (int)__builtin_ctzll(ballot(on && key == m) & kGrp);
-            d_lp = readlane_i(lpb, ds); d_ntu = readlane_i(ntu, ds); d_pk = readlane_i(pk, ds);
-            d_tot = readlane_i(tot, ds);
-            have_d = true;
-          }
-        }
-      }
-      // slot w: kept[w % nk] (cyclic pad, src/v2.rs:293-297 / src/lib.rs:163-167), the last slot
-      // the diagonal candidate when there is one (src/v2.rs:298-308)
-      int j = w;
-      while (j >= nk) j -= nk;
-      g_lp = bperm_i(j, r_lp);
-      g_ntu = bperm_i(j, r_ntu);
-      g_pk = bperm_i(j, r_pk);
-      g_tot = kV2 ? bperm_i(j, r_tot) : 0;
-      if constexpr (kV1 && STAGED) {
-        cv0 = __int_as_float(bperm_i(j, r_v0));
-        cv1 = __int_as_float(bperm_i(j, r_v1));
-      }
-      if (have_d && w == W - 1) {
-        g_lp = d_lp; g_ntu = d_ntu; g_pk = d_pk; g_tot = d_tot;
-      }
-    } else {
     // ---- stable descending rank (src/lib.rs:161): keys are unique, so ranks are a permutation
     const unsigned khi = lp_key(lp);
     // kSign (>= 32 compares per lane): a 63-bit key (high word shifted by 31), so a difference of
@@ -527,9 +438,6 @@ void k_fused_reg(FusedDecodeArgs a, int hist_lds) {
       if constexpr (kNW == 4) {
         const int4 pr = *reinterpret_cast<const int4*>(xr + lane * kNW);
         r16 = (pr.x + pr.y) + (pr.z + pr.w);
-      } else if constexpr (kNW == 2) {
-        const int2 pr = *reinterpret_cast<const int2*>(xr + lane * kNW);
-        r16 = pr.x + pr.y;
       } else {
         r16 = part << 4;  // (one wave: never called)
       }
@@ -548,13 +456,10 @@ void k_fused_reg(FusedDecodeArgs a, int hist_lds) {
       // replica r counts the keys [r JN, (r + 1) JN) of replica 0 that beat its candidate (reads
       // broadcast within the replica); the partial counts are summed across replicas by swapping
       // 16-lane rows and 32-lane halves
-      // (several waves: each wave counts JN / kNW of those keys, and the waves' partial counts
-      // are summed like the four-wave rank below)
       constexpr int JN = NMAX / kReps;
-      constexpr int JW = JN / kNW;
       keys[lane] = kSign ? 0ull - key : key;
       lds_order();
-      rank = count_beats(keys + (lane / NMAX) * JN + JW * wv, std::integral_constant<int, JW>{});
+      rank = count_beats(keys + (lane / NMAX) * JN, std::integral_constant<int, JN>{});
       lds_order();
       if constexpr (kReps == 4) {
         const auto r16 = __builtin_amdgcn_permlane16_swap(rank, rank, false, false);
@@ -562,10 +467,6 @@ void k_fused_reg(FusedDecodeArgs a, int hist_lds) {
       }
       const auto r32 = __builtin_amdgcn_permlane32_swap(rank, rank, false, false);
       rank = (int)(r32[0] + r32[1]);
-      if constexpr (kNW > 1) {
-        rank = wave_sum16(rank) >> 4;
-        rank16 = (gbase | rank) << 4;
-      }
     } else if constexpr (kNW > 1) {
       // wave wv counts the keys [16 wv, 16 wv + 16) of its own copy; the partial counts meet in
       // LDS (double-buffered by step parity: a wave a step ahead writes the other buffer) across
@@ -700,7 +601,6 @@ void k_fused_reg(FusedDecodeArgs a, int hist_lds) {
     if constexpr (kV1 && STAGED) {
       cv0 = __int_as_float(bperm_i(srcl, s_v0));
       cv1 = __int_as_float(bperm_i(srcl, s_v1));
-    }
     }
     }
     hist = __int_as_float(g_lp);
@@ -914,41 +814,10 @@ __global__ __launch_bounds__(64) void k_fused_paths(FusedDecodeArgs a) {
   if (bad && a.status) atomicOr(a.status, kStatusBadIndex);
 }
 
-inline int last_error() { return hipGetLastError() == hipSuccess ? SSNT_OK : SSNT_ERR_HIP; }
-
 constexpr size_t kMaxLds = 150 * 1024;
 
-// ordering of the register kernel's step: the full rank. The selection ordering (SEL) is
-// bit-identical and measured slower at every BASELINE shape; it is compiled
-// only into the A/B build (-DSSNT_AB: ssnt_fused_decode_select 0 full rank, 1 selection).
-// waves of tone's replicated rank (1, 2 or 4); the A/B build can override it per process. One:
-// at configs[4] two waves measured 202 us and four 215 us against 189 us for one
-// (profiles/r5b_tone_waves.json) -- the step's LDS round trips, not its 16 compares, set it
-constexpr int kToneWaves = 1;
-#ifdef SSNT_AB
-std::atomic<int> g_select{-1};
-bool use_select() { return g_select.load(std::memory_order_relaxed) == 1; }
-std::atomic<int> g_tone_waves{-1};
-int tone_waves() {
-  const int t = g_tone_waves.load(std::memory_order_relaxed);
-  return t > 0 ? t : kToneWaves;
-}
-#define SSNT_SEL_OR_RANK(sel, RANK, SELK) ((sel) ? (SELK) : (RANK))
-#else
-constexpr bool use_select() { return false; }
-constexpr int tone_waves() { return kToneWaves; }
-#define SSNT_SEL_OR_RANK(sel, RANK, SELK) (RANK)
-#endif
-
-template <typename K>
-int launch_with_lds(K kernel, size_t lds, int B, hipStream_t st, const FusedDecodeArgs& a,
-                    int extra, int waves = 1) {
-  if (lds > 64 * 1024)  // per launch: the attribute is per device, and cheap to set
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-  hipLaunchKernelGGL(kernel, dim3(B), dim3(64 * waves), lds, st, a, extra);
-  return last_error();
-}
+// The register kernel's step orders by the full rank. The selection ordering (SEL) is bit-identical
+// and measured slower at every BASELINE shape; retired to git history.
 
 template <Variant V>
 int launch_variant(const FusedDecodeArgs& a, hipStream_t st) {
@@ -959,10 +828,8 @@ int launch_variant(const FusedDecodeArgs& a, hipStream_t st) {
   int rc = SSNT_OK;
   if (n <= 64) {
     const bool staged = V != Variant::V1 || 2 * (size_t)a.U <= 64 * (size_t)kV1Regs;
-    const bool sel = use_select();
     const int nmax = n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64;
-    const int tw = V == Variant::Tone ? tone_waves() : 1;
-    const int nw = staged ? fused_waves(V, nmax, sel, tw) : 1;
+    const int nw = staged ? fused_waves(V, nmax) : 1;
     const bool whole = RegLayout(V, a.W, a.T, a.U, true, staged, true, nw).total <= kMaxLds;
     const bool hist_lds = whole || RegLayout(V, a.W, a.T, a.U, true, staged, false, nw).total <= kMaxLds;
     const size_t lds = RegLayout(V, a.W, a.T, a.U, hist_lds, staged, whole, nw).total;
@@ -972,24 +839,12 @@ int launch_variant(const FusedDecodeArgs& a, hipStream_t st) {
       constexpr int NM = decltype(kw)::value;
       constexpr bool WH = decltype(kc)::value;
       if (!staged) {  // only v1 rows can be too long to stage
-        if constexpr (V == Variant::V1) {
-          return SSNT_SEL_OR_RANK(sel, launch_with_lds(k_fused_reg<V, false, 64, WH, false>, lds, a.B, st, a, h),
-                                  launch_with_lds(k_fused_reg<V, false, 64, WH, true>, lds, a.B, st, a, h));
-        }
+        if constexpr (V == Variant::V1)
+          return launch_lds(k_fused_reg<V, false, 64, WH>, dim3(a.B), dim3(64), lds, kMaxLds, st, a, h);
         return (int)SSNT_ERR_UNSUPPORTED;
       }
-#ifdef SSNT_AB
-      if constexpr (V == Variant::Tone && NM == 32) {  // (A/B study forms; measured slower)
-        if (!sel && tw == 2)
-          return launch_with_lds(k_fused_reg<V, true, NM, WH, false, 2>, lds, a.B, st, a, h, 2);
-        if (!sel && tw == 4)
-          return launch_with_lds(k_fused_reg<V, true, NM, WH, false, 4>, lds, a.B, st, a, h, 4);
-      }
-#endif
-      return SSNT_SEL_OR_RANK(sel, launch_with_lds(k_fused_reg<V, true, NM, WH, false>, lds, a.B, st, a, h,
-                                                   fused_waves(V, NM, false)),
-                              launch_with_lds(k_fused_reg<V, true, NM, WH, true>, lds, a.B, st, a, h,
-                                              fused_waves(V, NM, true)));
+      return launch_lds(k_fused_reg<V, true, NM, WH>, dim3(a.B), dim3(64 * fused_waves(V, NM)), lds, kMaxLds,
+                        st, a, h);
     };
     auto pick = [&](auto kc) {
       if (n <= 8) return go(std::integral_constant<int, 8>{}, kc);
@@ -1003,16 +858,12 @@ int launch_variant(const FusedDecodeArgs& a, hipStream_t st) {
     const size_t lds = (size_t)n * sizeof(Cand) + 2 * (size_t)n * 4 + (size_t)a.W * 2 * 16 +
                        (V == Variant::V1 ? (size_t)a.W * 8 : 0) + 2 * (size_t)a.W + 16;
     if (lds > kMaxLds) return SSNT_ERR_UNSUPPORTED;
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_fused_lds<V>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    hipLaunchKernelGGL(k_fused_lds<V>, dim3(a.B), dim3(64), lds, st, a);
-    rc = last_error();
+    rc = launch_lds(k_fused_lds<V>, dim3(a.B), dim3(64), lds, kMaxLds, st, a);
   }
   if (rc != SSNT_OK || !paths_kernel) return rc;
   const int threads = a.B * a.W;
   hipLaunchKernelGGL(k_fused_paths, dim3((threads + 63) / 64), dim3(64), 0, st, a);
-  return last_error();
+  return launch_status();
 }
 
 }  // namespace
@@ -1028,19 +879,6 @@ int diag_decode_read(void* host, size_t bytes) {
   return -1;
 #endif
 }
-
-#ifdef SSNT_AB
-int set_fused_decode_select(int mode) {
-  if (mode < -1 || mode > 1) return SSNT_ERR_INVALID_ARG;
-  g_select.store(mode);
-  return SSNT_OK;
-}
-int set_fused_decode_tone_waves(int n) {
-  if (n != -1 && n != 1 && n != 2 && n != 4) return SSNT_ERR_INVALID_ARG;
-  g_tone_waves.store(n);
-  return SSNT_OK;
-}
-#endif
 
 int launch_fused_decode(const FusedDecodeArgs& a, hipStream_t st) {
   if (a.B < 0 || a.W <= 0 || a.T <= 0 || !a.src || !a.input_length || !a.prediction ||

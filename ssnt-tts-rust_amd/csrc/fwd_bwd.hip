@@ -27,6 +27,7 @@
 #include <mutex>
 
 #include "lattice_dev.h"
+#include "launch_util.h"
 
 namespace ssnt {
 namespace {
@@ -293,19 +294,11 @@ __global__ __launch_bounds__(128) void k_fwd_bwd(FwdBwdArgs a) {
   fill_rows(S);
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 template <int K, bool OBS, bool LDS, bool VEC>
 int launch_kernel(const FwdBwdArgs& a, size_t lds, hipStream_t st) {
   auto kern = k_fwd_bwd<K, OBS, LDS, VEC>;
   note_fwd_bwd_dispatch("k_fwd_bwd<K=%d,OBS=%d,LDS=%d,VEC=%d>", K, (int)OBS, (int)LDS, (int)VEC);
-  // dynamic LDS above 64 KiB needs the attribute; it is per device, so it is set on every such
-  // launch (a host-side call, no device work) rather than cached in a process-wide flag
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
-  hipLaunchKernelGGL(kern, dim3(a.B), dim3(128), lds, st, a);
-  return hipGetLastError() == hipSuccess ? SSNT_OK : SSNT_ERR_HIP;
+  return launch_lds(kern, dim3(a.B), dim3(128), lds, kLdsBudget, st, a);
 }
 
 template <int K, bool OBS>
@@ -316,9 +309,9 @@ int launch_k(const FwdBwdArgs& a, hipStream_t st) {
   if (!lds && (a.workspace == nullptr || a.workspace_bytes < fwd_bwd_workspace_bytes(a.B, a.T, a.U)))
     return SSNT_ERR_WORKSPACE;
   // whole lane slices (U % K == 0) and 16-byte aligned tensors -> widest branch-free accesses
-  const bool vec = (a.U % K == 0) && aligned16(a.log_trans) && aligned16(a.log_obs) &&
-                   aligned16(a.grad) && aligned16(a.grad_obs) && aligned16(a.log_alpha) &&
-                   aligned16(a.log_beta) && aligned16(a.workspace);
+  const bool vec = (a.U % K == 0) && aligned_to(a.log_trans, 16) && aligned_to(a.log_obs, 16) &&
+                   aligned_to(a.grad, 16) && aligned_to(a.grad_obs, 16) && aligned_to(a.log_alpha, 16) &&
+                   aligned_to(a.log_beta, 16) && aligned_to(a.workspace, 16);
   const size_t shm = lds ? head + rows : head;
   if (lds)
     return vec ? launch_kernel<K, OBS, true, true>(a, shm, st) : launch_kernel<K, OBS, true, false>(a, shm, st);
@@ -368,9 +361,8 @@ size_t fwd_bwd_workspace_bytes(int B, int T, int U) {
   // 0 when the default dispatch keeps every row in LDS whatever the call brings: U <= 256, the
   // streaming kernel's rows fit beside its rings with or without log_obs and with the narrow
   // form's padded rows, and the two-wave kernel (what takes 4-byte-aligned tensors)
-  // fits its rows too. (The A/B build's forced segmented kernel, pair kernel and deep rings
-  // always get the workspace.)
-  if (variant() == 0 && stream_ring() == 0 && U <= 256) {
+  // fits its rows too. (The A/B build's forced segmented kernel always gets the workspace.)
+  if (variant() == 0 && U <= 256) {
     const int K = U <= 64 ? 1 : U <= 128 ? 2 : 4;
     const size_t Up = (size_t)K * ((U + K - 1) / K);
     const size_t rows = (size_t)T * Up * sizeof(xf);
@@ -493,7 +485,7 @@ int launch_fwd_bwd_debug64(const FwdBwdArgs& a0, double* loss64, double* la64, d
   const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 + 1 : 4096);
   hipLaunchKernelGGL(k_debug64, dim3(blocks), dim3(256), 0, st, am, ae, bm, be, n, la64, lb64, zs,
                      l32, a.B, loss64);
-  return hipGetLastError() == hipSuccess ? SSNT_OK : SSNT_ERR_HIP;
+  return launch_status();
 }
 
 size_t fwd_bwd_sum_state_bytes(int B) { return kSumGranuleOffset + 8 * (size_t)(B > 0 ? B : 0); }
@@ -515,7 +507,7 @@ int launch_fwd_bwd(const FwdBwdArgs& a, hipStream_t st) {
   const size_t n = strlen(t_dispatch);
   snprintf(t_dispatch + n, sizeof t_dispatch - n, "+k_loss_sum");
   hipLaunchKernelGGL(k_loss_sum, dim3(1), dim3(64), 0, st, a.loss, a.B, a.loss_sum);
-  return hipGetLastError() == hipSuccess ? SSNT_OK : SSNT_ERR_HIP;
+  return launch_status();
 }
 
 }  // namespace ssnt

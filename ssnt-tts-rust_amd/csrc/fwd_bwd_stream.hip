@@ -38,11 +38,11 @@
 #include <string.h>
 #include <limits.h>
 
-#include <atomic>
 #include <type_traits>
 #include <utility>
 
 #include "lattice_dev.h"
+#include "launch_util.h"
 #include "stream_dev.h"
 
 namespace ssnt {
@@ -53,19 +53,19 @@ template <bool OBS>
 constexpr int in_slots() { return OBS ? 4 : 8; }  // converted-row ring slots per direction
 template <bool OBS>
 constexpr int out_slots() { return OBS ? 4 : 8; }  // chain-row ring (rows past the cut) per direction
-template <bool OBS>
-constexpr int kChainPrefetch(int R) { return R >= 16 ? 4 : 2; }  // factor rows in flight per chain
+constexpr int kChainPrefetch = 2;  // factor rows in flight per chain
 template <int K>
 constexpr int conv_depth() { return K <= 2 ? 8 : (K <= 4 ? 4 : 2); }  // converter prefetch rows
 
 // DBG: debug rows requested (log_alpha / log_beta, f32 logs or the raw split-exponent state of
 // ssnt_fwd_bwd_debug64_device) -- a separate instance, so the product's carries neither the
 // debug path nor its pointers (their SGPRs spilled into VGPR lanes in the hot loops)
-template <int K, bool OBS, bool LDS, int kNC, int kNH, int kRingSel, bool NV, bool DBG>
+// Ring depth: deep rings (16 / 32 slots, rows in the workspace) measured slower;
+// retired to git history.
+template <int K, bool OBS, bool LDS, int kNC, int kNH, bool NV, bool DBG>
 __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream(FwdBwdArgs a) {
   constexpr int kWaves = 2 + 2 * kNC + 2 * kNH;
-  // kRingSel: ring slots (0 = default; 16 / 32: the A/B build's deep rings)
-  constexpr int R = kRingSel ? kRingSel : in_slots<OBS>();
+  constexpr int R = in_slots<OBS>();
   constexpr int kR2 = out_slots<OBS>() < R ? out_slots<OBS>() : R;
   static_assert(R % kR2 == 0, "ring sizes");
 #ifdef SSNT_DIAG
@@ -559,7 +559,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
     if (check) tag_check(&ctl->ctag[d][j], row, a.status);
 #endif
   };
-  constexpr int PF = kChainPrefetch<OBS>(R);  // rows of factors in flight per chain
+  constexpr int PF = kChainPrefetch;  // rows of factors in flight per chain
   static_assert(R % PF == 0 && PF < R, "prefetch buffers tile the ring");
   XRow<K> Eb[PF], Xb[PF], Ob[PF];
   // Steps run in half-blocks of H = R/2 (unrolled by R: slot offsets compile-time). All waits
@@ -570,21 +570,21 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
   // Phase 2 (past the cut) publishes every H2 steps instead: there the gradient waves read each
   // factor slot right behind the chain and the converters need it back, so the hand-off
   // chain -> gradient waves -> converters -> chain has to close within the ring's slack.
-  using H1 = std::integral_constant<int, (R >= 16 ? R / 4 : R / 2)>;
-  using H2 = std::integral_constant<int, (R >= 16 ? R / 8 : (R / 4 > 2 ? R / 4 : 2))>;
+  using H1 = std::integral_constant<int, R / 2>;
+  using H2 = std::integral_constant<int, (R / 4 > 2 ? R / 4 : 2)>;
   auto run = [&](auto Hc, int lo, int hi, auto&& step, auto&& hwait) {
     constexpr int HS = decltype(Hc)::value;
     static_assert(R % HS == 0, "sub-blocks tile the ring");
     for (int base = lo & ~(R - 1); base < hi; base += R) {
-      sfor<R / HS>([&](auto Q) {
+      static_for<R / HS>([&](auto Q) {
         constexpr int h0 = decltype(Q)::value * HS;
         const int hb0 = base + h0;
         if (hb0 + HS <= lo || hb0 >= hi) return;
         hwait(max(hb0, lo), min(hb0 + HS, hi));
         if (hb0 >= lo && hb0 + HS <= hi) {
-          sfor<HS>([&](auto J) { step(std::integral_constant<int, h0 + decltype(J)::value>{}, base, true); });
+          static_for<HS>([&](auto J) { step(std::integral_constant<int, h0 + decltype(J)::value>{}, base, true); });
         } else {
-          sfor<HS>([&](auto J) {
+          static_for<HS>([&](auto J) {
             constexpr int j = decltype(J)::value;
             step(std::integral_constant<int, h0 + j>{}, base, hb0 + j >= lo && hb0 + j < hi);
           });
@@ -601,7 +601,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
     const int last = max(n - 1, 0);  // last stream row the chain reads
     wait_row(min(PF - 1, last));
     cbar();
-    sfor<PF>([&](auto J) {
+    static_for<PF>([&](auto J) {
       constexpr int j = decltype(J)::value;
       rd(j, Eb[j], Xb[j], Ob[j], j, j <= last && n > 0);
     });
@@ -660,7 +660,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
     const int last = S - 1;
     wait_row(min(PF, last));
     cbar();
-    sfor<PF>([&](auto J) {
+    static_for<PF>([&](auto J) {
       constexpr int j = decltype(J)::value;
       rd(j, Eb[j], Xb[j], Ob[j], j, j <= last);
     });
@@ -734,68 +734,48 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
   dg.flush(b, role.slot);
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool aligned_to(const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & (m - 1)) == 0; }
-
-template <int K, bool OBS, bool LDS, int NC, int NH, int RS, bool NV>
+template <int K, bool OBS, bool LDS, int NC, int NH, bool NV>
 int launch_stream_kernel(const FwdBwdArgs& a, size_t lds, hipStream_t st) {
   const bool dbg = a.log_alpha || a.log_beta;
-  auto kern = dbg ? k_fwd_bwd_stream<K, OBS, LDS, NC, NH, RS, NV, true>
-                  : k_fwd_bwd_stream<K, OBS, LDS, NC, NH, RS, NV, false>;
-  note_fwd_bwd_dispatch("k_fwd_bwd_stream<K=%d,OBS=%d,LDS=%d,NC=%d,NH=%d,RS=%d,NV=%d%s>", K, (int)OBS,
-                        (int)LDS, NC, NH, RS, (int)NV, dbg ? ",DBG" : "");
-  // dynamic LDS above 64 KiB needs the attribute; it is per device, so it is set on every such
-  // launch (a host-side call, no device work) rather than cached in a process-wide flag
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
-  hipLaunchKernelGGL(kern, dim3(a.B), dim3(64 * (2 + 2 * NC + 2 * NH)), lds, st, a);
-  return hipGetLastError() == hipSuccess ? SSNT_OK : SSNT_ERR_HIP;
+  auto kern = dbg ? k_fwd_bwd_stream<K, OBS, LDS, NC, NH, NV, true>
+                  : k_fwd_bwd_stream<K, OBS, LDS, NC, NH, NV, false>;
+  note_fwd_bwd_dispatch("k_fwd_bwd_stream<K=%d,OBS=%d,LDS=%d,NC=%d,NH=%d,NV=%d%s>", K, (int)OBS,
+                        (int)LDS, NC, NH, (int)NV, dbg ? ",DBG" : "");
+  return launch_lds(kern, dim3(a.B), dim3(64 * (2 + 2 * NC + 2 * NH)), lds, kLdsBudget, st, a);
 }
 
-template <int K, bool OBS, int NC, int NH, int RS = 0>
-int launch_stream_k(const FwdBwdArgs& a, hipStream_t st, bool force_ws = false) {
+template <int K, bool OBS, int NC, int NH>
+int launch_stream_k(const FwdBwdArgs& a, hipStream_t st) {
   // whole lane slices and 16-byte aligned tensors: the vector form; else (U % K != 0, or
   // tensors at 4-byte alignment) the narrow form: one 8-byte access per (emit, shift) position,
   // which buffer loads and stores take at any dword alignment (a sliced log_trans / grad at an
   // odd float offset no longer drops to the two-wave kernel)
-  const bool vec = (a.U % K == 0) && aligned16(a.log_trans) && aligned16(a.log_obs) &&
-                   aligned16(a.grad) && aligned16(a.grad_obs) && aligned16(a.log_alpha) &&
-                   aligned16(a.log_beta) && aligned16(a.workspace);
-  const bool narrow_ok = aligned_to(a.log_trans, 4) && aligned_to(a.grad, 4) && aligned16(a.workspace) &&
+  const bool vec = (a.U % K == 0) && aligned_to(a.log_trans, 16) && aligned_to(a.log_obs, 16) &&
+                   aligned_to(a.grad, 16) && aligned_to(a.grad_obs, 16) && aligned_to(a.log_alpha, 16) &&
+                   aligned_to(a.log_beta, 16) && aligned_to(a.workspace, 16);
+  const bool narrow_ok = aligned_to(a.log_trans, 4) && aligned_to(a.grad, 4) && aligned_to(a.workspace, 16) &&
                          aligned_to(a.log_obs, 4) && aligned_to(a.grad_obs, 4) &&
                          aligned_to(a.log_alpha, 4) && aligned_to(a.log_beta, 4);
   if (!vec && !narrow_ok) return SSNT_ERR_UNSUPPORTED;
   const int Up = K * ((a.U + K - 1) / K);
-  const size_t head = stream_head_bytes(K, a.U, OBS, RS);
+  const size_t head = stream_head_bytes(K, a.U, OBS);
   if (head > kLdsBudget) return SSNT_ERR_UNSUPPORTED;
   const size_t rows = (size_t)a.T * (vec ? a.U : Up) * sizeof(xf);
-  const bool lds = !force_ws && head + rows <= kLdsBudget;
+  const bool lds = head + rows <= kLdsBudget;
   if (!lds && (a.workspace == nullptr || a.workspace_bytes < (size_t)a.B * rows))
     return SSNT_ERR_WORKSPACE;
   if (vec)
-    return lds ? launch_stream_kernel<K, OBS, true, NC, NH, RS, false>(a, head + rows, st)
-               : launch_stream_kernel<K, OBS, false, NC, NH, RS, false>(a, head, st);
-  return lds ? launch_stream_kernel<K, OBS, true, NC, NH, RS, true>(a, head + rows, st)
-             : launch_stream_kernel<K, OBS, false, NC, NH, RS, true>(a, head, st);
+    return lds ? launch_stream_kernel<K, OBS, true, NC, NH, false>(a, head + rows, st)
+               : launch_stream_kernel<K, OBS, false, NC, NH, false>(a, head, st);
+  return lds ? launch_stream_kernel<K, OBS, true, NC, NH, true>(a, head + rows, st)
+             : launch_stream_kernel<K, OBS, false, NC, NH, true>(a, head, st);
 }
-
-#ifdef SSNT_AB
-std::atomic<int> g_ring{0};  // A/B build: 0 default rings; 16 / 32 ring slots with workspace rows (K = 2)
-#endif
 
 template <bool OBS>
 int launch_stream_obs(const FwdBwdArgs& a, hipStream_t st) {
   // wave mix per lane width: 16 waves (3 converters + 4 gradient waves per direction) while a
   // wave fits 128 VGPRs (K <= 2); 10 waves for K >= 4 (168 VGPRs, no spills)
   if (a.U <= 64) return launch_stream_k<1, OBS, 3, 4>(a, st);
-#ifdef SSNT_AB
-  if constexpr (!OBS) {  // A/B build (ssnt_fwd_bwd_stream_ring): deeper rings, rows in the workspace
-    const int ring = g_ring.load(std::memory_order_relaxed);
-    if (a.U > 64 && a.U <= 128 && ring == 16) return launch_stream_k<2, false, 3, 4, 16>(a, st, true);
-    if (a.U > 64 && a.U <= 128 && ring == 32) return launch_stream_k<2, false, 3, 4, 32>(a, st, true);
-  }
-#endif
   if (a.U <= 128) return launch_stream_k<2, OBS, 3, 4>(a, st);
   if (a.U <= 256) return launch_stream_k<4, OBS, 2, 2>(a, st);
   // K = 8 (U <= 512, configs[4]): the two-wave kernel. The streaming kernel needs 4-slot rings to
@@ -817,8 +797,8 @@ int diag_read(void* host, size_t bytes) {
 #endif
 }
 
-size_t stream_head_bytes(int K, int U, bool obs, int ring) {
-  const int R = ring ? ring : obs ? in_slots<true>() : in_slots<false>();
+size_t stream_head_bytes(int K, int U, bool obs) {
+  const int R = obs ? in_slots<true>() : in_slots<false>();
   const int R2o = obs ? out_slots<true>() : out_slots<false>();
   const int R2 = R2o < R ? R2o : R;
   const size_t Up = (size_t)K * ((U + K - 1) / K);  // (= U when U % K == 0)
@@ -830,14 +810,5 @@ size_t stream_head_bytes(int K, int U, bool obs, int ring) {
 int launch_fwd_bwd_stream(const FwdBwdArgs& a, hipStream_t st) {
   return a.log_obs ? launch_stream_obs<true>(a, st) : launch_stream_obs<false>(a, st);
 }
-
-#ifdef SSNT_AB
-int set_stream_ring(int r) {
-  if (r != 0 && r != 16 && r != 32) return SSNT_ERR_INVALID_ARG;
-  g_ring.store(r);
-  return SSNT_OK;
-}
-int stream_ring() { return g_ring.load(std::memory_order_relaxed); }
-#endif
 
 }  // namespace ssnt

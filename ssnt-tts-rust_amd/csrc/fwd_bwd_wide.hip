@@ -44,6 +44,7 @@
 #include <utility>
 
 #include "lattice_dev.h"
+#include "launch_util.h"
 
 namespace ssnt {
 namespace {
@@ -96,16 +97,6 @@ struct WideGrid {
 __device__ __forceinline__ int gctr_ld(const int* p) {
   return __builtin_amdgcn_readfirstlane(
       __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-
-// compile-time loop: f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>)
-template <typename F, int... I>
-__device__ __forceinline__ void wfor_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void sfor(F&& f) {
-  wfor_impl(f, std::make_integer_sequence<int, N>{});
 }
 
 __device__ __forceinline__ int wctr_ld(const int* p) {
@@ -425,7 +416,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * (kMaxNW / 2 + 1 + (CONV ? kMaxNW / 2 :
       const int ws = pub ? 1 : 0;
       // one straight-line path for every block (steps past n are dead: their stores are
       // dropped): no join of two paths, so no register copies of rows with loads in flight
-      sfor<kBS>([&](auto Kc) __attribute__((always_inline)) {
+      static_for<kBS>([&](auto Kc) __attribute__((always_inline)) {
         constexpr int k = decltype(Kc)::value;
         float pm;
         int pe;
@@ -520,7 +511,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * (kMaxNW / 2 + 1 + (CONV ? kMaxNW / 2 :
     for (int k = 0; k < kBS; ++k) load_item(rowof(k), cr[k]);
     f32x4* fr = &fring[cw * kFR * 64];
     for (int i0 = 0; i0 < n; i0 += kBS) {
-      sfor<kBS>([&](auto Kc) __attribute__((always_inline)) {
+      static_for<kBS>([&](auto Kc) __attribute__((always_inline)) {
         constexpr int k = decltype(Kc)::value;
         if constexpr (k % kSub == 0) {
           wait_ge(&ctl.ccons[cw], i0 + k + kSub - kFR, a.status);
@@ -939,7 +930,8 @@ inline WideLayout wide_layout(int B, int T, int U) {
 
 // -1 auto (default): split when the unsplit grid would leave most CUs idle (8B <= CUs), or when
 // the split grid fits the chip (4B <= CUs) and the lattice is long (T >= 640) -- measured per
-// shape; 0 never; 1 whenever NW >= 2; 2 (A/B study) phase 2 only
+// shape; 0 never; 1 whenever NW >= 2. (Splitting phase 2 only, +SPLIT2, measured
+// slower -- DESIGN.md 5.2 -- and was retired to git history.)
 #ifdef SSNT_AB
 std::atomic<int> g_wide_split{-1};  // A/B build: ssnt_fwd_bwd_wide_split
 int wide_split_mode() { return g_wide_split.load(std::memory_order_relaxed); }
@@ -987,14 +979,6 @@ int launch_wide(const FwdBwdArgs& a, hipStream_t st) {
     // profiles/r5i_split_shapes.jsonl)
     split = 8 * a.B <= cus || (4 * a.B <= cus && a.T >= 640);
   }
-  if (NW >= 2 && mode == 2) {  // A/B study: phase 1 in one workgroup per direction, phase 2 split
-    if (hipMemsetAsync(gd.ctr, 0, l.ctr, st) != hipSuccess) return SSNT_ERR_HIP;
-    note_fwd_bwd_dispatch("k_fwd_bwd_wide<K=%d,OBS=%d,DBG=%d,NW=%d>+SPLIT2", K, (int)OBS, (int)DBG, NW);
-    hipLaunchKernelGGL((k_fwd_bwd_wide<K, OBS, 1, DBG, false>), dim3(a.B, 2), dim3(64 * NW), 0, st, a, gd);
-    if (hipGetLastError() != hipSuccess) return SSNT_ERR_HIP;
-    hipLaunchKernelGGL((k_fwd_bwd_wide<K, OBS, 2, DBG, true>), dim3(4 * a.B), dim3(64 * (gd.NWp + 1)), 0, st, a, gd);
-    return hipGetLastError() == hipSuccess ? SSNT_OK : SSNT_ERR_HIP;
-  }
   if (split) {
     if (hipMemsetAsync(gd.ctr, 0, l.ctr, st) != hipSuccess) return SSNT_ERR_HIP;
     const dim3 grid(4 * a.B), block(64 * (gd.NWp + 1));
@@ -1005,16 +989,16 @@ int launch_wide(const FwdBwdArgs& a, hipStream_t st) {
       hipLaunchKernelGGL((k_fwd_bwd_wide<K, OBS, 1, DBG, true, true>), grid, dim3(64 * (2 * gd.NWp + 1)), 0, st, a, gd);
     else
       hipLaunchKernelGGL((k_fwd_bwd_wide<K, OBS, 1, DBG, true>), grid, block, 0, st, a, gd);
-    if (hipGetLastError() != hipSuccess) return SSNT_ERR_HIP;
+    if (launch_status() != SSNT_OK) return SSNT_ERR_HIP;
     hipLaunchKernelGGL((k_fwd_bwd_wide<K, OBS, 2, DBG, true>), grid, block, 0, st, a, gd);
-    return hipGetLastError() == hipSuccess ? SSNT_OK : SSNT_ERR_HIP;
+    return launch_status();
   }
   const dim3 grid(a.B, 2), block(64 * NW);
   note_fwd_bwd_dispatch("k_fwd_bwd_wide<K=%d,OBS=%d,DBG=%d,NW=%d>x2", K, (int)OBS, (int)DBG, NW);
   hipLaunchKernelGGL((k_fwd_bwd_wide<K, OBS, 1, DBG, false>), grid, block, 0, st, a, gd);
-  if (hipGetLastError() != hipSuccess) return SSNT_ERR_HIP;
+  if (launch_status() != SSNT_OK) return SSNT_ERR_HIP;
   hipLaunchKernelGGL((k_fwd_bwd_wide<K, OBS, 2, DBG, false>), grid, block, 0, st, a, gd);
-  return hipGetLastError() == hipSuccess ? SSNT_OK : SSNT_ERR_HIP;
+  return launch_status();
 }
 
 template <int K>
@@ -1042,9 +1026,9 @@ size_t fwd_bwd_wide_workspace_bytes(int B, int T, int U) {
 int launch_fwd_bwd_wide(const FwdBwdArgs& a, hipStream_t st, bool any_u) {
   if ((!any_u && a.U <= 256) || a.U > 64 * 2 * kMaxNW) return SSNT_ERR_UNSUPPORTED;
   // 8-byte granules: every tensor base must be 8-byte aligned (4 for the f32-element ones)
-  auto al = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & (m - 1)) == 0; };
-  if (!al(a.log_trans, 8) || !al(a.grad, 8) || !al(a.workspace, 8) || !al(a.log_obs, 4) ||
-      !al(a.grad_obs, 4) || !al(a.log_alpha, 4) || !al(a.log_beta, 4))
+  if (!aligned_to(a.log_trans, 8) || !aligned_to(a.grad, 8) || !aligned_to(a.workspace, 8) ||
+      !aligned_to(a.log_obs, 4) || !aligned_to(a.grad_obs, 4) || !aligned_to(a.log_alpha, 4) ||
+      !aligned_to(a.log_beta, 4))
     return SSNT_ERR_UNSUPPORTED;
   if (!a.workspace || a.workspace_bytes < fwd_bwd_wide_workspace_bytes(a.B, a.T, a.U))
     return SSNT_ERR_WORKSPACE;
@@ -1062,7 +1046,7 @@ int set_fwd_bwd_wide_lanes(int k) {
 }
 
 int set_fwd_bwd_wide_split(int mode) {
-  if (mode < -1 || mode > 2) return SSNT_ERR_INVALID_ARG;
+  if (mode < -1 || mode > 1) return SSNT_ERR_INVALID_ARG;
   g_wide_split.store(mode);
   return SSNT_OK;
 }

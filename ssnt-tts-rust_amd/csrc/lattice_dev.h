@@ -356,11 +356,6 @@ __device__ __forceinline__ void beta_step(XRow<K>& Bt, const XRow<K>& E, const X
   }
 }
 
-// raw buffer over [base, base+bytes): out-of-range lanes read 0 / drop their stores.
-// `base` must be wave-uniform (the descriptor lives in SGPRs).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t brsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
-}
 // N floats at byte offset voff of a buffer range
 template <int N>
 __device__ __forceinline__ void buf_ld(float* dst, __amdgpu_buffer_rsrc_t r, int voff) {

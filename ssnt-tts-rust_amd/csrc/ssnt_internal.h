@@ -57,20 +57,14 @@ int launch_fwd_bwd_stream(const FwdBwdArgs& a, hipStream_t stream);
 // any_u; SSNT_ERR_UNSUPPORTED for other shapes
 int launch_fwd_bwd_wide(const FwdBwdArgs& a, hipStream_t stream, bool any_u);
 size_t fwd_bwd_wide_workspace_bytes(int B, int T, int U);
-size_t stream_head_bytes(int K, int U, bool obs, int ring = 0);  // LDS bytes besides the lattice rows
+size_t stream_head_bytes(int K, int U, bool obs);  // LDS bytes besides the lattice rows
 // Process-wide A/B knobs and the kernels only they reach: the A/B build (-DSSNT_AB, `make
 // lib-ab`, lib/ab/libssnt_tts_c_ab.so; tests and tools) only. The product dispatches by shape.
 #ifdef SSNT_AB
 int set_fwd_bwd_variant(int v);
-int set_stream_ring(int r);  // 0 default, 16 / 32 ring slots with workspace rows
-int stream_ring();
 int set_fwd_bwd_wide_lanes(int k);  // positions per lane of the long-row kernel (1 or 2)
 int set_fwd_bwd_wide_split(int mode);  // two workgroups per direction (-1 auto, 0 off, 1 on)
 int set_fwd_bwd_wide_lag(int sleeps);  // split form: downstream wave 0 idles per block (race test)
-int set_fused_decode_select(int mode);  // -1 default, 0 full rank, 1 selection
-int set_fused_decode_tone_waves(int n);  // -1 default, 1 / 2 / 4 waves for tone's rank
-#else
-constexpr int stream_ring() { return 0; }
 #endif
 int diag_read(void* host, size_t bytes);  // -DSSNT_DIAG builds only (tools/diag_fwd_bwd.py)
 // the fwd-bwd kernel instance this thread dispatched last ("k_fwd_bwd_stream<K=2,...>"; one

@@ -140,16 +140,6 @@ __device__ __forceinline__ int first_missing(const int* cnt, int begin) {
   return m;
 }
 
-// compile-time loop: f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>)
-template <typename F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void sfor(F&& f) {
-  sfor_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 // Wave roles: chains, converters, gradient waves, in wave order. The hardware places wave w of
 // a workgroup on SIMD (base + w) % 4 (measured, tools/micro/micro_simd.hip), so this order
 // spreads each role over all four SIMDs. (Tried: giving each chain a SIMD shared only with

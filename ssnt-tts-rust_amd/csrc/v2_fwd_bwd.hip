@@ -29,6 +29,7 @@
 #include <limits.h>
 
 #include "buffer_ops.h"
+#include "launch_util.h"
 #include "ssnt_internal.h"
 #include "xf_math.h"
 
@@ -283,8 +284,7 @@ __device__ __forceinline__ void f4_sweep(const V2FwdBwdArgs& a, unsigned char* s
   float pre[NPF];
   // class log-probs through one descriptor: masked entries read past its end (zeros), so the
   // loads need no exec mask and no default writes into registers with loads in flight
-  const __amdgpu_buffer_rsrc_t lg_r = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(lg), (short)0, (int)((size_t)Imax * D * sizeof(float)), 0x00020000);
+  const __amdgpu_buffer_rsrc_t lg_r = brsrc(lg, (unsigned)((size_t)Imax * D * sizeof(float)));
   auto load_chunk = [&](int c) {  // chunk c = sweep steps [c CH, (c + 1) CH): class log-probs
 #pragma unroll
     for (int j = 0; j < NPF; ++j) {
@@ -325,8 +325,7 @@ __device__ __forceinline__ void f4_sweep(const V2FwdBwdArgs& a, unsigned char* s
   if (la) f4_log_row(la, rw(0), 0, 0, X);
   // the utterance's workspace rows through one buffer descriptor (32-bit offsets: no 64-bit
   // address arithmetic per cell)
-  const __amdgpu_buffer_rsrc_t ws_r = __builtin_amdgcn_make_buffer_rsrc(
-      ws, (short)0, (int)((size_t)(Imax + 1) * Wc * sizeof(xf)), 0x00020000);
+  const __amdgpu_buffer_rsrc_t ws_r = brsrc(ws, (unsigned)((size_t)(Imax + 1) * Wc * sizeof(xf)));
   // the windows of 64 consecutive steps, one per lane (lane l: the row of step 64 j + l), formed
   // once per block; a step reads the next step's window with two v_readlane instead of the
   // f32 band arithmetic and its branches (the same rule, f4_window, evaluated per lane)
@@ -589,17 +588,10 @@ size_t v2_fwd_bwd_workspace_bytes(int B, int Imax, int max_total, bool test_mode
 
 template <int DC>
 int launch_f4(const V2FwdBwdArgs& a, size_t lds, size_t glds, hipStream_t st) {
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_f4_sweep<DC>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k_f4_sweep<DC>, dim3(a.B, 2), dim3(kF4Threads), lds, st, a);
-  if (hipGetLastError() != hipSuccess) return SSNT_ERR_HIP;
-  if (!a.grad && !a.log_beta) return SSNT_OK;
-  if (glds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_f4_grad<DC>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds);
-  hipLaunchKernelGGL(k_f4_grad<DC>, dim3(a.B, a.Imax + 1), dim3(f4_grad_threads<DC>()), glds, st, a);
-  return hipGetLastError() == hipSuccess ? SSNT_OK : SSNT_ERR_HIP;
+  // (each launch raises its own attribute to what it asks for)
+  const int rc = launch_lds(k_f4_sweep<DC>, dim3(a.B, 2), dim3(kF4Threads), lds, lds, st, a);
+  if (rc != SSNT_OK || (!a.grad && !a.log_beta)) return rc;
+  return launch_lds(k_f4_grad<DC>, dim3(a.B, a.Imax + 1), dim3(f4_grad_threads<DC>()), glds, glds, st, a);
 }
 
 int launch_v2_fwd_bwd(const V2FwdBwdArgs& in, hipStream_t st) {

@@ -31,6 +31,7 @@
 #include <utility>
 
 #include "lattice_dev.h"
+#include "launch_util.h"
 
 namespace ssnt {
 namespace {
@@ -55,17 +56,6 @@ __device__ __forceinline__ float shr1_ninf(float x) {
 // v_writelane_b32: lane `lane` of the result holds the wave-uniform `v`, the other lanes keep `old`
 // (bound to the LLVM intrinsic by name, as buffer_ops.h does: this toolchain has no clang builtin)
 extern "C" __device__ int vit_writelane(int v, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
-
-// f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>): unrolled in the source, so the
-// per-unit register arrays are split into scalars before any loop pass sees them
-template <class F, int... I>
-__device__ __forceinline__ void vit_each(F& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void vit_for(F f) {
-  vit_each(f, std::make_integer_sequence<int, N>{});
-}
 
 struct VitShared {
   int feasible, s, p;
@@ -184,7 +174,7 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
     const int ppu = q.vec ? 2 : 1;                       // positions per log_trans unit
     const int upr = (U + 64 * ppu - 1) / (64 * ppu);     // units per row and lane
     const int upro = (U + 63) / 64;
-    vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+    static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
       constexpr int u = decltype(Ic)::value;
       const int row = w + kVitLoaders * (u / upr);
       const int p = (lane + 64 * (u % upr)) * ppu;
@@ -206,12 +196,12 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
     const int n = min(R, S - 1 - r0);
     const __amdgpu_buffer_rsrc_t rs = brsrc(lt + (size_t)r0 * U * 2, (unsigned)(n * U) * 8u);
     if (q.vec) {
-      vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
         lreg[u] = rbuf_ld4(rs, goff[u], 0, 0);
       });
     } else {
-      vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
         const f32x2 v = rbuf_ld2(rs, goff[u], 0, 0);
         lreg[u].x = v.x; lreg[u].y = v.y;
@@ -219,7 +209,7 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
     }
     if constexpr (OBS) {  // log_obs rows [c*R + 1, ...): the row a step adds is its own
       const __amdgpu_buffer_rsrc_t ro = brsrc(lo + (size_t)(r0 + 1) * U, (unsigned)(n * U) * 4u);
-      vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
         oreg[u] = rbuf_ld1(ro, goffo[u], 0, 0);
       });
@@ -229,20 +219,20 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
   auto commit = [&](int c) __attribute__((always_inline)) {
     float2* dst = ltb + (size_t)(c & 1) * bufsz;
     if (q.vec) {
-      vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
         dst[loff[u]] = make_float2(lreg[u].x, lreg[u].y);
         dst[loff[u] + (K == 1 ? 1 : kKs)] = make_float2(lreg[u].z, lreg[u].w);
       });
     } else {
-      vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
         dst[loff[u]] = make_float2(lreg[u].x, lreg[u].y);
       });
     }
     if constexpr (OBS) {
       float* dsto = obb + (size_t)(c & 1) * bufsz;
-      vit_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
         dsto[loffo[u]] = oreg[u];
       });
@@ -416,8 +406,6 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
     }
 }
 
-inline bool vit_aligned(const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & (m - 1)) == 0; }
-
 template <int K, bool OBS, int MODE>
 int launch_viterbi_k(const ViterbiArgs& a, const VitLayout& L, bool vec, hipStream_t st) {
   VitParams q{};
@@ -425,12 +413,7 @@ int launch_viterbi_k(const ViterbiArgs& a, const VitLayout& L, bool vec, hipStre
   q.vec = vec;
   q.start_off = (unsigned)L.start_off; q.lt_off = (unsigned)L.lt_off;
   q.ob_off = (unsigned)L.ob_off; q.bits_off = (unsigned)L.bits_off;
-  auto kern = k_viterbi<K, OBS, MODE>;
-  if (L.total > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
-  hipLaunchKernelGGL(kern, dim3(a.B), dim3(kVitThreads), L.total, st, a, q);
-  return hipGetLastError() == hipSuccess ? SSNT_OK : SSNT_ERR_HIP;
+  return launch_lds(k_viterbi<K, OBS, MODE>, dim3(a.B), dim3(kVitThreads), L.total, kLdsBudget, st, a, q);
 }
 
 template <int K, bool OBS>
@@ -463,17 +446,17 @@ int launch_viterbi(const ViterbiArgs& a, hipStream_t st) {
   if (a.B == 0) return SSNT_OK;
   if (!a.log_trans || !a.step_len || !a.pos_len || !a.log_prob) return SSNT_ERR_INVALID_ARG;
   if (a.U > 1024) return SSNT_ERR_UNSUPPORTED;
-  if (!vit_aligned(a.log_trans, 8) || !vit_aligned(a.log_obs, 4)) return SSNT_ERR_UNSUPPORTED;
+  if (!aligned_to(a.log_trans, 8) || !aligned_to(a.log_obs, 4)) return SSNT_ERR_UNSUPPORTED;
   const bool path = a.position || a.duration;
   const bool obs = a.log_obs != nullptr;
   const int U = a.U > 0 ? a.U : 1;  // (T == 0 or U == 0: every utterance is infeasible)
   const bool fit = a.T == 0 || a.U == 0 || vit_bits_fit(a.T, U);
   if (path && !fit) {
     const size_t need = viterbi_workspace_bytes(a.B, a.T, a.U);
-    if (!a.workspace || a.workspace_bytes < need || !vit_aligned(a.workspace, 8)) return SSNT_ERR_WORKSPACE;
+    if (!a.workspace || a.workspace_bytes < need || !aligned_to(a.workspace, 8)) return SSNT_ERR_WORKSPACE;
   }
   const int mode = !path ? 0 : fit ? 1 : 2;
-  const bool vec = vit_aligned(a.log_trans, 16) && U % 2 == 0;
+  const bool vec = aligned_to(a.log_trans, 16) && U % 2 == 0;
   const VitLayout L = vit_pick(a.T, U, vec && !obs, obs, mode);
   if (L.total > kLdsBudget) return SSNT_ERR_UNSUPPORTED;
   return obs ? launch_viterbi_obs<true>(a, L, vec, mode, st) : launch_viterbi_obs<false>(a, L, vec, mode, st);

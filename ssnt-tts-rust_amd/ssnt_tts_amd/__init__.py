@@ -269,6 +269,33 @@ def _sum_state(dev, B):
     return t
 
 
+def _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit, zero_infinity=False):
+    """The checked device tensors (lt, sl, pl, lo) of a call on the emit/shift lattice and its
+    flags word."""
+    lt = _dev(log_trans, torch.float32, "log_trans")
+    B, T, U, two = lt.shape
+    if two != 2:
+        raise ValueError("log_trans must be (B,T,U,2)")
+    sl = _dev(step_len, torch.int32, "step_len").reshape(B)
+    pl = _dev(pos_len, torch.int32, "pos_len").reshape(B)
+    lo = None if log_obs is None else _dev(log_obs, torch.float32, "log_obs").reshape(B, T, U)
+    flags = (FLAG_TERMINAL_EMIT if terminal_emit else 0) | (FLAG_ZERO_INFINITY if zero_infinity else 0)
+    return lt, sl, pl, lo, flags
+
+
+def _buf(out, dev, key, shape, dtype, want=True, name=None):
+    """Output tensor `key`: the caller's out[key] when given (checked), else a new one; None
+    when not wanted. `name` is how the dtype reads in the error message."""
+    if not want:
+        return None
+    t = out.get(key)
+    if t is None:
+        t = torch.empty(shape, dtype=dtype, device=dev)
+    elif tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"out[{key!r}] must be a contiguous {name or dtype} tensor of shape {shape}")
+    return t
+
+
 def ssnt_fwd_bwd(log_trans, step_len, pos_len, log_obs=None, *, terminal_emit=True,
                  zero_infinity=False, need_grad=True, debug=False, check=False, out=None,
                  loss_sum=False, debug64=False):
@@ -293,32 +320,17 @@ def ssnt_fwd_bwd(log_trans, step_len, pos_len, log_obs=None, *, terminal_emit=Tr
         return _fwd_bwd_debug64(log_trans, step_len, pos_len, log_obs, terminal_emit,
                                 zero_infinity, need_grad, check)
     lib = load(require_gpu=True)
-    lt = _dev(log_trans, torch.float32, "log_trans")
+    lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit,
+                                            zero_infinity)
     dev = lt.device
-    B, T, U, two = lt.shape
-    if two != 2:
-        raise ValueError("log_trans must be (B,T,U,2)")
-    sl = _dev(step_len, torch.int32, "step_len").reshape(B)
-    pl = _dev(pos_len, torch.int32, "pos_len").reshape(B)
-    lo = None if log_obs is None else _dev(log_obs, torch.float32, "log_obs").reshape(B, T, U)
-    flags = (FLAG_TERMINAL_EMIT if terminal_emit else 0) | (FLAG_ZERO_INFINITY if zero_infinity else 0)
+    B, T, U, _ = lt.shape
     out = dict(out or {})
-
-    def _buf(key, shape, want):
-        if not want:
-            return None
-        t = out.get(key)
-        if t is None:
-            t = torch.empty(shape, dtype=torch.float32, device=dev)
-        elif tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"out[{key!r}] must be a contiguous float32 tensor of shape {shape}")
-        return t
-
-    loss = _buf("loss", (B,), True)
-    grad = _buf("grad", (B, T, U, 2), need_grad)
-    gobs = _buf("grad_obs", (B, T, U), need_grad and lo is not None)
-    la = _buf("log_alpha", (B, T, U), debug)
-    lb = _buf("log_beta", (B, T, U), debug)
+    f32 = {"dtype": torch.float32, "name": "float32"}
+    loss = _buf(out, dev, "loss", (B,), **f32)
+    grad = _buf(out, dev, "grad", (B, T, U, 2), want=need_grad, **f32)
+    gobs = _buf(out, dev, "grad_obs", (B, T, U), want=need_grad and lo is not None, **f32)
+    la = _buf(out, dev, "log_alpha", (B, T, U), want=debug, **f32)
+    lb = _buf(out, dev, "log_beta", (B, T, U), want=debug, **f32)
     wsb = int(lib.ssnt_fwd_bwd_workspace_size(B, T, U))
     ws = _workspace(dev, wsb)
     st = out.get("status")
@@ -327,7 +339,7 @@ def ssnt_fwd_bwd(log_trans, step_len, pos_len, log_obs=None, *, terminal_emit=Tr
     else:
         st.zero_()
     if loss_sum:
-        lsum = _buf("loss_sum", (1,), True)
+        lsum = _buf(out, dev, "loss_sum", (1,), **f32)
         rc = lib.ssnt_fwd_bwd_sum_device(_p(lt), _p(lo), _p(sl), _p(pl), B, T, U, flags, _p(loss),
                                          _p(grad), _p(gobs), _p(la), _p(lb), _p(ws), wsb, _p(st),
                                          _p(lsum), _p(_sum_state(dev, B)), _stream(dev))
@@ -352,20 +364,15 @@ def ssnt_fwd_bwd(log_trans, step_len, pos_len, log_obs=None, *, terminal_emit=Tr
 def _fwd_bwd_debug64(log_trans, step_len, pos_len, log_obs, terminal_emit, zero_infinity,
                      need_grad, check):
     lib = load(require_gpu=True)
-    lt = _dev(log_trans, torch.float32, "log_trans")
+    lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit,
+                                            zero_infinity)
     dev = lt.device
-    B, T, U, two = lt.shape
-    if two != 2:
-        raise ValueError("log_trans must be (B,T,U,2)")
-    sl = _dev(step_len, torch.int32, "step_len").reshape(B)
-    pl = _dev(pos_len, torch.int32, "pos_len").reshape(B)
-    lo = None if log_obs is None else _dev(log_obs, torch.float32, "log_obs").reshape(B, T, U)
-    flags = (FLAG_TERMINAL_EMIT if terminal_emit else 0) | (FLAG_ZERO_INFINITY if zero_infinity else 0)
-    loss = torch.empty((B,), dtype=torch.float64, device=dev)
-    la = torch.empty((B, T, U), dtype=torch.float64, device=dev)
-    lb = torch.empty((B, T, U), dtype=torch.float64, device=dev)
-    grad = torch.empty((B, T, U, 2), dtype=torch.float32, device=dev) if need_grad else None
-    gobs = torch.empty((B, T, U), dtype=torch.float32, device=dev) if need_grad and lo is not None else None
+    B, T, U, _ = lt.shape
+    loss = _buf({}, dev, "loss", (B,), torch.float64)
+    la = _buf({}, dev, "log_alpha", (B, T, U), torch.float64)
+    lb = _buf({}, dev, "log_beta", (B, T, U), torch.float64)
+    grad = _buf({}, dev, "grad", (B, T, U, 2), torch.float32, want=need_grad)
+    gobs = _buf({}, dev, "grad_obs", (B, T, U), torch.float32, want=need_grad and lo is not None)
     wsb = int(lib.ssnt_fwd_bwd_debug64_workspace_size(B, T, U))
     ws = _workspace(dev, wsb)
     st = _status(dev)
@@ -392,30 +399,13 @@ def ssnt_viterbi_align(log_trans, step_len, pos_len, log_obs=None, *, terminal_e
     the emit. ``need_path=False`` computes ``log_prob`` only. ``out`` may pass preallocated
     tensors under the same keys."""
     lib = load(require_gpu=True)
-    lt = _dev(log_trans, torch.float32, "log_trans")
+    lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit)
     dev = lt.device
-    B, T, U, two = lt.shape
-    if two != 2:
-        raise ValueError("log_trans must be (B,T,U,2)")
-    sl = _dev(step_len, torch.int32, "step_len").reshape(B)
-    pl = _dev(pos_len, torch.int32, "pos_len").reshape(B)
-    lo = None if log_obs is None else _dev(log_obs, torch.float32, "log_obs").reshape(B, T, U)
-    flags = FLAG_TERMINAL_EMIT if terminal_emit else 0
+    B, T, U, _ = lt.shape
     out = dict(out or {})
-
-    def _buf(key, shape, dtype, want):
-        if not want:
-            return None
-        t = out.get(key)
-        if t is None:
-            t = torch.empty(shape, dtype=dtype, device=dev)
-        elif tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
-            raise ValueError(f"out[{key!r}] must be a contiguous {dtype} tensor of shape {shape}")
-        return t
-
-    lp = _buf("log_prob", (B,), torch.float32, True)
-    pos = _buf("position", (B, T), torch.int32, need_path)
-    dur = _buf("duration", (B, U), torch.int32, need_path)
+    lp = _buf(out, dev, "log_prob", (B,), torch.float32)
+    pos = _buf(out, dev, "position", (B, T), torch.int32, want=need_path)
+    dur = _buf(out, dev, "duration", (B, U), torch.int32, want=need_path)
     wsb = int(lib.ssnt_viterbi_align_workspace_size(B, T, U)) if need_path else 0
     ws = _workspace(dev, wsb)
     st = out.get("status")

@@ -26,16 +26,11 @@ def _eq(gpu_out, ref, keys, ctx=""):
         assert np.array_equal(g, ref[k]), f"{ctx} {k}: gpu={g} ref={ref[k]}"
 
 
-@pytest.fixture(params=[pytest.param(0, id="rank"), pytest.param(1, marks=pytest.mark.ab, id="select")])
+@pytest.fixture(params=[pytest.param(0, id="rank")])
 def select_mode(request, gpu):
-    """The fused decodes' two step orderings (full rank: the product; selection: forced through
-    the A/B build, include/ssnt_tts_c_ab.h) must give identical outputs."""
-    if request.param == 0:
-        yield 0
-        return
-    with gpu.use_ab() as ab:
-        assert ab.ssnt_fused_decode_select(1) == 0
-        yield 1
+    """The fused decodes' step ordering: the full rank. (The selection ordering, once forced
+    through the A/B build as a second param, is retired; the `rank` id keeps the node ids.)"""
+    yield 0
 
 
 @pytest.fixture(params=[pytest.param(0, marks=pytest.mark.ab, id="sync"),

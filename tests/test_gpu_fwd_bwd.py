@@ -282,8 +282,7 @@ def test_config5_long_form_bit_exact(gpu, oracle):
 
 
 @pytest.fixture(params=[pytest.param((1, 1), id="K1"), pytest.param((1, 0), id="K1-one-wg"),
-                        pytest.param((2, 1), id="K2"), pytest.param((2, 0), id="K2-one-wg"),
-                        pytest.param((1, 2), id="K1-split2", marks=pytest.mark.ab)])
+                        pytest.param((2, 1), id="K2"), pytest.param((2, 0), id="K2-one-wg")])
 def wide_lanes(request, gpu):
     """The long-row kernel's two lane widths (positions per lane), each with a direction's
     segments split over two workgroups (global hand-off) and in one workgroup, must be
@@ -327,7 +326,7 @@ def test_wide_rows_product_instance(gpu, oracle, wide_lanes, shape):
     P = [min(U, T)] + [int(x) for x in rng.integers(1, min(U, T) + 1, size=B - 1)]
     S = [T] + [int(rng.integers(p, T + 1)) for p in P[1:]]
     g = _run_gpu(gpu, lt, S, P, debug=False)
-    if wide_lanes == 1 and ",SPLIT" in gpu.last_fwd_bwd_kernel():  # (the split form; not +SPLIT2)
+    if wide_lanes == 1 and ",SPLIT" in gpu.last_fwd_bwd_kernel():  # (the split form)
         assert "CONV" in gpu.last_fwd_bwd_kernel(), gpu.last_fwd_bwd_kernel()
     o = oracle.fwd_bwd_xf(lt, S, P)
     _assert_bit_exact(g, o, ["loss", "grad"])
@@ -662,26 +661,6 @@ def test_rows_beyond_512_live_ragged_batch(gpu, oracle, wide_lanes, kernel_varia
     g = _run_gpu(gpu, lt, S, P)
     o = oracle.fwd_bwd_xf(lt, S, P, debug=True)
     _assert_bit_exact(g, o, ["loss", "grad", "log_alpha", "log_beta"])
-
-
-@pytest.mark.ab
-@pytest.mark.parametrize("ring", [16, 32])
-def test_stream_ring_depth_variants(gpu, oracle, kernel_variant, ring):
-    # the streaming kernel's deeper-ring A/B form (16 / 32 factor slots, rows in the workspace)
-    # must be bit-identical to the oracle (ragged batch, debug rows)
-    if kernel_variant != 0:
-        pytest.skip("a streaming-kernel form")
-    with gpu.use_ab() as ab:
-        assert ab.ssnt_fwd_bwd_stream_ring(ring) == 0
-        rng = np.random.default_rng(ring)
-        B, T, U = 6, 200, 80
-        lt = oracle.synth_log_trans(B, T, U, seed=ring)
-        P = [U] + [int(x) for x in rng.integers(1, U + 1, size=B - 1)]
-        S = [T] + [int(rng.integers(p, T + 1)) for p in P[1:]]
-        g = _run_gpu(gpu, lt, S, P)
-        assert f"RS={ring}" in gpu.last_fwd_bwd_kernel() and "LDS=0" in gpu.last_fwd_bwd_kernel()
-        o = oracle.fwd_bwd_xf(lt, S, P, debug=True)
-        _assert_bit_exact(g, o, ["loss", "grad", "log_alpha", "log_beta"])
 
 
 _TAG_SCRIPT = r"""

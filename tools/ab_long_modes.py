@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """configs[4] fwd-bwd (B=64 T=2000 U=400) through the A/B build: the segmented kernel with each
-direction in one workgroup (split 0), split over two workgroups (1) and split in phase 2 only (2),
-alternating rounds; outputs bit-identical across forms. One JSON line per form (median HIP event
+direction in one workgroup (split 0) and split over two workgroups (1), alternating rounds; outputs bit-identical across forms. One JSON line per form (median HIP event
 time per call). Run under rocprofv3 --kernel-trace --stats for the per-phase kernel times."""
 import json
 import sys
@@ -15,10 +14,10 @@ sys.path.insert(0, str(ROOT / "ssnt-tts-rust_amd"))
 import ssnt_tts_amd as S  # noqa: E402
 
 # args: [B T U] form... -- a form is "<split>" or "<split>k2" (two positions per lane:
-# ssnt_fwd_bwd_wide_lanes(2)); default configs[4] and forms 0 1 2
+# ssnt_fwd_bwd_wide_lanes(2)); default configs[4] and forms 0 1
 args = sys.argv[1:]
 B, T, U = (int(x) for x in args[:3]) if len(args) >= 3 and int(args[0]) > 2 else (64, 2000, 400)
-modes = (args[3:] if len(args) >= 3 and int(args[0]) > 2 else args) or ["0", "1", "2"]
+modes = (args[3:] if len(args) >= 3 and int(args[0]) > 2 else args) or ["0", "1"]
 
 
 def set_form(ab, m):
