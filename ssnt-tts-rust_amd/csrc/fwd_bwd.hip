@@ -1,4 +1,5 @@
-// fwd_bwd.hip -- emit/shift lattice forward-backward (loss + gradients) for gfx950.
+// fwd_bwd.hip -- emit/shift lattice forward-backward (loss + gradients) for gfx950: the two-wave
+// kernel, the fallback of the dispatcher (fwd_bwd_dispatch.hip); shared device code: lattice_dev.h.
 //
 // Lattice semantics: DESIGN.md "Lattice semantics" (SURVEY.md 8(a) A11). The reference
 // (nii-yamagishilab/ssnt-tts-rust) has no forward-backward; the transition rules come from its
@@ -18,13 +19,6 @@
 //   stream out while the recurrence is still running.
 // Arithmetic: split-exponent xf (xf_math.h); bit-exact with oracle/ssnt_oracle.c.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <atomic>
-#include <mutex>
 
 #include "lattice_dev.h"
 #include "launch_util.h"
@@ -102,15 +96,9 @@ __global__ __launch_bounds__(128) void k_fwd_bwd(FwdBwdArgs a) {
       X.e[j] = XF_EZERO;
     }
     if (lane == 0) {
-      if constexpr (OBS) {
-        const xf o = xf_exp(lo[0], true);
-        const xf n = xf_norm(o.m, o.e);
-        X.m[0] = n.m;
-        X.e[0] = n.e;
-      } else {
-        X.m[0] = 0.5f;
-        X.e[0] = 1;
-      }
+      const xf a0 = alpha0<OBS>(lo);
+      X.m[0] = a0.m;
+      X.e[0] = a0.e;
     }
     store_row<K, VEC>(rows, X, U, lane);
     if (la) store_dbg_row<K, VEC>(la, lae, X, U, lane);
@@ -175,7 +163,8 @@ __global__ __launch_bounds__(128) void k_fwd_bwd(FwdBwdArgs a) {
       wm[j] = X.m[j] * c.m;
       we[j] = X.e[j] + c.e;
     }
-    // in-lane binary tree (pairs (2i,2i+1) first)
+    // in-lane binary tree (pairs (2i,2i+1) first), then the xor butterfly; the same lines stand in
+    // fwd_bwd_stream.hip and fwd_bwd_wide.hip (a shared function: this kernel 98.7 vs 95.6 us)
 #pragma unroll
     for (int len = K; len > 1; len >>= 1) {
 #pragma unroll
@@ -185,11 +174,10 @@ __global__ __launch_bounds__(128) void k_fwd_bwd(FwdBwdArgs a) {
         we[i] = r.e;
       }
     }
+    // (K == 1: the normalization is overwritten at once, yet without these lines two K = 1
+    // instances compile differently, one with 52 instead of 20 bytes of scratch: they stay)
     xf z = (K == 1) ? xf_norm(wm[0], we[0]) : xf{wm[0], we[0]};
-    if (K == 1) {  // level 1 of the tree happens across lanes: first combine leaves
-      // (K == 1: the leaves are per-lane; the xor-1 butterfly below is level 1)
-      z = xf{wm[0], we[0]};
-    }
+    if (K == 1) z = xf{wm[0], we[0]};
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
       const float om = __shfl_xor(z.m, off);
@@ -296,218 +284,43 @@ __global__ __launch_bounds__(128) void k_fwd_bwd(FwdBwdArgs a) {
 
 template <int K, bool OBS, bool LDS, bool VEC>
 int launch_kernel(const FwdBwdArgs& a, size_t lds, hipStream_t st) {
-  auto kern = k_fwd_bwd<K, OBS, LDS, VEC>;
   note_fwd_bwd_dispatch("k_fwd_bwd<K=%d,OBS=%d,LDS=%d,VEC=%d>", K, (int)OBS, (int)LDS, (int)VEC);
-  return launch_lds(kern, dim3(a.B), dim3(128), lds, kLdsBudget, st, a);
+  return launch_lds(k_fwd_bwd<K, OBS, LDS, VEC>, dim3(a.B), dim3(128), lds, kLdsBudget, st, a);
 }
 
 template <int K, bool OBS>
-int launch_k(const FwdBwdArgs& a, hipStream_t st) {
-  const size_t head = (size_t)(64 * K + 2) * sizeof(xf);
-  const size_t rows = (size_t)a.T * a.U * sizeof(xf);
-  const bool lds = head + rows <= kLdsBudget;
-  if (!lds && (a.workspace == nullptr || a.workspace_bytes < fwd_bwd_workspace_bytes(a.B, a.T, a.U)))
+int launch_k(const FwdBwdArgs& a, const RowsPlan& p, hipStream_t st) {
+  if (!p.lds && (a.workspace == nullptr || a.workspace_bytes < fwd_bwd_workspace_bytes(a.B, a.T, a.U)))
     return SSNT_ERR_WORKSPACE;
-  // whole lane slices (U % K == 0) and 16-byte aligned tensors -> widest branch-free accesses
-  const bool vec = (a.U % K == 0) && aligned_to(a.log_trans, 16) && aligned_to(a.log_obs, 16) &&
-                   aligned_to(a.grad, 16) && aligned_to(a.grad_obs, 16) && aligned_to(a.log_alpha, 16) &&
-                   aligned_to(a.log_beta, 16) && aligned_to(a.workspace, 16);
-  const size_t shm = lds ? head + rows : head;
-  if (lds)
-    return vec ? launch_kernel<K, OBS, true, true>(a, shm, st) : launch_kernel<K, OBS, true, false>(a, shm, st);
-  return vec ? launch_kernel<K, OBS, false, true>(a, shm, st) : launch_kernel<K, OBS, false, false>(a, shm, st);
+  const bool vec = (a.U % K == 0) && all_aligned(a, 16, 16, 16);
+  if (p.lds)
+    return vec ? launch_kernel<K, OBS, true, true>(a, p.shm_bytes, st) : launch_kernel<K, OBS, true, false>(a, p.shm_bytes, st);
+  return vec ? launch_kernel<K, OBS, false, true>(a, p.shm_bytes, st) : launch_kernel<K, OBS, false, false>(a, p.shm_bytes, st);
 }
 template <bool OBS>
-int launch_simple(const FwdBwdArgs& a, hipStream_t st) {
-  if (a.U <= 64) return launch_k<1, OBS>(a, st);
-  if (a.U <= 128) return launch_k<2, OBS>(a, st);
-  if (a.U <= 256) return launch_k<4, OBS>(a, st);
-  if (a.U <= 512) return launch_k<8, OBS>(a, st);
-  return SSNT_ERR_UNSUPPORTED;
+int launch_obs(const FwdBwdArgs& a, const RowsPlan& p, hipStream_t st) {
+  if (p.K == 1) return launch_k<1, OBS>(a, p, st);
+  if (p.K == 2) return launch_k<2, OBS>(a, p, st);
+  return p.K == 4 ? launch_k<4, OBS>(a, p, st) : launch_k<8, OBS>(a, p, st);
 }
-
-// Kernel choice. The product dispatches by shape only (the streaming kernel, else the segmented
-// kernel, else the two-wave kernel). The A/B build (-DSSNT_AB, `make lib-ab`; tests and tools
-// only) adds a process-wide override: 1 two-wave kernel only, 2 segmented kernel;
-// SSNT_FWD_BWD_KERNEL=simple selects 1 there. (The pair and rows kernels of rounds 2-4, both
-// bit-exact and measured slower -- DESIGN.md 5.1a / 5.1c -- were retired to git history.)
-#ifdef SSNT_AB
-std::atomic<int> g_variant{0};
-std::once_flag g_variant_env;
-int variant() {
-  std::call_once(g_variant_env, [] {
-    const char* e = getenv("SSNT_FWD_BWD_KERNEL");
-    if (e && strcmp(e, "simple") == 0) g_variant.store(1);
-  });
-  return g_variant.load(std::memory_order_relaxed);
-}
-#else
-constexpr int variant() { return 0; }
-#endif
-
-thread_local char t_dispatch[160];
 
 }  // namespace
 
-void note_fwd_bwd_dispatch(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(t_dispatch, sizeof t_dispatch, fmt, ap);
-  va_end(ap);
-}
-const char* last_fwd_bwd_dispatch() { return t_dispatch; }
-
-size_t fwd_bwd_workspace_bytes(int B, int T, int U) {
-  // 0 when the default dispatch keeps every row in LDS whatever the call brings: U <= 256, the
-  // streaming kernel's rows fit beside its rings with or without log_obs and with the narrow
-  // form's padded rows, and the two-wave kernel (what takes 4-byte-aligned tensors)
-  // fits its rows too. (The A/B build's forced segmented kernel always gets the workspace.)
-  if (variant() == 0 && U <= 256) {
-    const int K = U <= 64 ? 1 : U <= 128 ? 2 : 4;
-    const size_t Up = (size_t)K * ((U + K - 1) / K);
-    const size_t rows = (size_t)T * Up * sizeof(xf);
-    // (log_obs rings carry wider slots, the ones without more of them: take the larger head)
-    const size_t h0 = stream_head_bytes(K, U, false), h1 = stream_head_bytes(K, U, true);
-    const bool stream_lds = (h0 > h1 ? h0 : h1) + rows <= kLdsBudget;
-    const bool simple_lds = (size_t)(64 * K + 2) * sizeof(xf) + (size_t)T * U * sizeof(xf) <= kLdsBudget;
-    if (stream_lds && simple_lds) return 0;
-  }
-  // the segmented kernel keeps its rows (plus beta at the cut) in the workspace at every T; one
-  // size serves every kernel (the two-wave kernel needs B*T*U xf at most; the streaming
-  // kernel's narrow form pads rows to whole lane slices: U + 3 at most)
-  const size_t wide = fwd_bwd_wide_workspace_bytes(B, T, U);
-  const size_t stream = (size_t)B * T * ((size_t)U + 3) * sizeof(xf);
-  return wide > stream ? wide : stream;
+// cut buffer (64K xf) + Z broadcast, then the rows [T][U] when they fit
+RowsPlan simple_plan(int T, int U) {
+  RowsPlan p{};
+  p.K = lanes_for(U);
+  const size_t head = (size_t)(64 * p.K + 2) * sizeof(xf), rows = (size_t)T * U * sizeof(xf);
+  p.supported = p.K != 0;
+  p.lds = head + rows <= kLdsBudget;
+  p.shm_bytes = p.lds ? head + rows : head;
+  return p;
 }
 
-#ifdef SSNT_AB
-int set_fwd_bwd_variant(int v) {
-  // 0 default dispatch, 1 two-wave kernel, 2 segmented kernel at every U it takes
-  if (v < 0 || v > 2) return SSNT_ERR_INVALID_ARG;
-  variant();  // the environment is read once, before any explicit choice
-  g_variant.store(v);
-  return SSNT_OK;
-}
-#endif
-
-namespace {
-__global__ __launch_bounds__(64) void k_loss_sum(const float* loss, int B, float* out) {
-  const float sum = wave_loss_sum(loss, B);
-  if (threadIdx.x == 0) *out = sum;
-}
-
-int launch_variant(const FwdBwdArgs& a, hipStream_t st, bool& summed) {
-  summed = false;
-  if (variant() == 0) {
-    FwdBwdArgs x = a;
-    if (!a.sum_state) x.loss_sum = nullptr;
-    int rc = launch_fwd_bwd_stream(x, st);
-    summed = x.loss_sum != nullptr;
-    if (rc != SSNT_ERR_UNSUPPORTED) return rc;
-    summed = false;
-    // long rows, and what the streaming kernel declines (4-byte-aligned log_trans / grad): the
-    // segmented kernel takes any U <= 1024 at 8-byte alignment (loss sum: the separate pass)
-    if (a.workspace && a.workspace_bytes >= fwd_bwd_wide_workspace_bytes(a.B, a.T, a.U)) {
-      rc = launch_fwd_bwd_wide(a, st, true);
-      if (rc != SSNT_ERR_UNSUPPORTED) return rc;
-    }
-  } else if (variant() == 2) {
-    const int rc = launch_fwd_bwd_wide(a, st, true);
-    if (rc != SSNT_ERR_UNSUPPORTED) return rc;
-  }
-  FwdBwdArgs x = a;
-  x.loss_sum = nullptr;  // the two-wave kernel only writes loss[]
-  return a.log_obs ? launch_simple<true>(x, st) : launch_simple<false>(x, st);
-}
-}  // namespace
-
-// ---- float64 debug outputs (ssnt_fwd_bwd_debug64_device) -------------------------------------
-// The kernels run in raw-state mode: mantissa / exponent planes of alpha and beta and Z per
-// utterance land in the workspace; this pass forms e*ln2 + ln(m) in float64 (zero mantissa:
-// -inf; loss: -ln Z, or the f32 kernel's +inf / 0 where Z was never formed or is 0).
-__global__ __launch_bounds__(256) void k_debug64(const float* am, const int* ae, const float* bm,
-                                                 const int* be, size_t n, double* la, double* lb,
-                                                 const float* zs, const float* loss32, int B,
-                                                 double* loss) {
-  constexpr double kLn2 = 0x1.62e42fefa39efp-1;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    if (la) la[i] = am[i] == 0.0f ? -__builtin_inf() : (double)ae[i] * kLn2 + log((double)am[i]);
-    if (lb) lb[i] = bm[i] == 0.0f ? -__builtin_inf() : (double)be[i] * kLn2 + log((double)bm[i]);
-  }
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)B; i += stride) {
-    const float zm = zs[2 * i];
-    const int ze = __builtin_bit_cast(int, zs[2 * i + 1]);
-    loss[i] = zm == 0.0f ? (double)loss32[i] : -((double)ze * kLn2 + log((double)zm));
-  }
-}
-
-namespace {
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-}  // namespace
-
-size_t fwd_bwd_debug64_workspace_bytes(int B, int T, int U) {
-  const size_t cells = (size_t)B * T * U;
-  return al256(fwd_bwd_workspace_bytes(B, T, U)) + 4 * al256(cells * 4) + al256((size_t)B * 8) +
-         al256((size_t)B * 4);
-}
-
-int launch_fwd_bwd_debug64(const FwdBwdArgs& a0, double* loss64, double* la64, double* lb64,
-                           hipStream_t st) {
-  if (a0.B < 0 || a0.T <= 0 || a0.U <= 0 || !loss64 || a0.loss_sum) return SSNT_ERR_INVALID_ARG;
-  if (a0.B == 0) return SSNT_OK;
-  const size_t need = fwd_bwd_debug64_workspace_bytes(a0.B, a0.T, a0.U);
-  if (!a0.workspace || a0.workspace_bytes < need) return SSNT_ERR_WORKSPACE;
-  const size_t cells = (size_t)a0.B * a0.T * a0.U;
-  const size_t base = fwd_bwd_workspace_bytes(a0.B, a0.T, a0.U);
-  unsigned char* w = static_cast<unsigned char*>(a0.workspace);
-  size_t off = al256(base);
-  auto take = [&](size_t bytes) { unsigned char* p = w + off; off += al256(bytes); return p; };
-  float* am = reinterpret_cast<float*>(take(cells * 4));
-  int* ae = reinterpret_cast<int*>(take(cells * 4));
-  float* bm = reinterpret_cast<float*>(take(cells * 4));
-  int* be = reinterpret_cast<int*>(take(cells * 4));
-  float* zs = reinterpret_cast<float*>(take((size_t)a0.B * 8));
-  float* l32 = reinterpret_cast<float*>(take((size_t)a0.B * 4));
-  FwdBwdArgs a = a0;
-  a.workspace = base ? a0.workspace : nullptr;  // the product dispatch sees the plain call's workspace
-  a.workspace_bytes = base;
-  a.loss = l32;
-  a.log_alpha = am;
-  a.log_beta = bm;
-  a.log_alpha_e = ae;
-  a.log_beta_e = be;
-  a.z_state = zs;
-  if (hipMemsetAsync(zs, 0, (size_t)a.B * 8, st) != hipSuccess) return SSNT_ERR_HIP;
-  int rc = launch_fwd_bwd(a, st);
-  if (rc != SSNT_OK) return rc;
-  const size_t n = la64 || lb64 ? cells : 0;
-  const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 + 1 : 4096);
-  hipLaunchKernelGGL(k_debug64, dim3(blocks), dim3(256), 0, st, am, ae, bm, be, n, la64, lb64, zs,
-                     l32, a.B, loss64);
-  return launch_status();
-}
-
-size_t fwd_bwd_sum_state_bytes(int B) { return kSumGranuleOffset + 8 * (size_t)(B > 0 ? B : 0); }
-
-int launch_fwd_bwd(const FwdBwdArgs& a, hipStream_t st) {
-  t_dispatch[0] = 0;  // (an argument error or an empty batch dispatches nothing)
-  if (a.B < 0 || a.T <= 0 || a.U <= 0 || !a.log_trans || !a.step_len || !a.pos_len || !a.loss)
-    return SSNT_ERR_INVALID_ARG;
-  if (a.grad_obs && !a.log_obs) return SSNT_ERR_INVALID_ARG;
-  if (a.B == 0) {
-    if (a.loss_sum) return hipMemsetAsync(a.loss_sum, 0, sizeof(float), st) == hipSuccess ? SSNT_OK : SSNT_ERR_HIP;
-    return SSNT_OK;
-  }
-  // batch loss sum: inside the streaming kernel when the caller gives a sum state, else one
-  // extra single-wave pass over loss[] (same fixed order, same bits)
-  bool summed = false;
-  const int rc = launch_variant(a, st, summed);
-  if (rc != SSNT_OK || !a.loss_sum || summed) return rc;
-  const size_t n = strlen(t_dispatch);
-  snprintf(t_dispatch + n, sizeof t_dispatch - n, "+k_loss_sum");
-  hipLaunchKernelGGL(k_loss_sum, dim3(1), dim3(64), 0, st, a.loss, a.B, a.loss_sum);
-  return launch_status();
+int launch_fwd_bwd_simple(const FwdBwdArgs& a, hipStream_t st) {
+  const RowsPlan p = simple_plan(a.T, a.U);
+  if (!p.supported) return SSNT_ERR_UNSUPPORTED;
+  return a.log_obs ? launch_obs<true>(a, p, st) : launch_obs<false>(a, p, st);
 }
 
 }  // namespace ssnt

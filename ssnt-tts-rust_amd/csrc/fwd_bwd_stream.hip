@@ -35,9 +35,8 @@
 // Lanes past U (p0 = K*lane >= U) read a clamped valid position and write to a junk area; their
 // values never reach a valid position except multiplied by a masked (exact zero) factor.
 #include <hip/hip_runtime.h>
-#include <string.h>
-#include <limits.h>
 
+#include <algorithm>
 #include <type_traits>
 #include <utility>
 
@@ -47,7 +46,6 @@
 
 namespace ssnt {
 namespace {
-
 
 template <bool OBS>
 constexpr int in_slots() { return OBS ? 4 : 8; }  // converted-row ring slots per direction
@@ -156,21 +154,13 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
     }
   };
   // converted-input slot j of direction d: per position (E.m, E.e, X.m, X.e); obs block after
-
-
   if (threadIdx.x < kCtlBytes / 4) reinterpret_cast<int*>(smem)[threadIdx.x] = 0;
   XRow<K> X = xrow_zero<K>();
   if (role.kind == 0 && role.d == 0) {  // alpha[0]: 1 at p = 0 (x obs[0][0])
     if (lane == 0) {
-      if constexpr (OBS) {
-        const xf o = xf_exp(lo[0], true);
-        const xf n = xf_norm(o.m, o.e);
-        X.m[0] = n.m;
-        X.e[0] = n.e;
-      } else {
-        X.m[0] = 0.5f;
-        X.e[0] = 1;
-      }
+      const xf a0 = alpha0<OBS>(lo);
+      X.m[0] = a0.m;
+      X.e[0] = a0.e;
     }
     row_st(0, X);
   }
@@ -194,7 +184,8 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
       const int r = hb + h + kNH * i;
       return d == 0 ? r : S - 1 - r;
     };
-    // ---- Z at the cut: tree-sum over p of alpha[M][p] * beta[M][p] (fixed order, = oracle)
+    // ---- Z at the cut: tree-sum over p of alpha[M][p] * beta[M][p] (fixed order, = oracle; the
+    // tree's lines also stand in fwd_bwd.hip and fwd_bwd_wide.hip: change the three together)
     if (d == 0 && h == 0) {
       const unsigned tag = a.loss_sum ? sum_tag(a) : 0u;  // (load in flight while waiting)
       spin_until<true>([&] { return ctr_acq(&ctl->a_ready); }, 1, a.status, dg);
@@ -226,11 +217,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
       }
       if (lane == 0) {
         ctl->z = z;
-        publish_loss(a, b, (z.m == 0.0f) ? inf_loss : 0.0f - xf_log(z), tag);
-        if (DBG && a.z_state) {
-          a.z_state[2 * b] = z.m;
-          a.z_state[2 * b + 1] = __builtin_bit_cast(float, z.e);
-        }
+        publish_z<true, DBG>(a, b, z, inf_loss, tag);
       }
       ctr_rel(&ctl->z_ready, 1);
     } else {
@@ -745,42 +732,27 @@ int launch_stream_kernel(const FwdBwdArgs& a, size_t lds, hipStream_t st) {
 }
 
 template <int K, bool OBS, int NC, int NH>
-int launch_stream_k(const FwdBwdArgs& a, hipStream_t st) {
+int launch_stream_k(const FwdBwdArgs& a, const RowsPlan& p, hipStream_t st) {
   // whole lane slices and 16-byte aligned tensors: the vector form; else (U % K != 0, or
   // tensors at 4-byte alignment) the narrow form: one 8-byte access per (emit, shift) position,
-  // which buffer loads and stores take at any dword alignment (a sliced log_trans / grad at an
-  // odd float offset no longer drops to the two-wave kernel)
-  const bool vec = (a.U % K == 0) && aligned_to(a.log_trans, 16) && aligned_to(a.log_obs, 16) &&
-                   aligned_to(a.grad, 16) && aligned_to(a.grad_obs, 16) && aligned_to(a.log_alpha, 16) &&
-                   aligned_to(a.log_beta, 16) && aligned_to(a.workspace, 16);
-  const bool narrow_ok = aligned_to(a.log_trans, 4) && aligned_to(a.grad, 4) && aligned_to(a.workspace, 16) &&
-                         aligned_to(a.log_obs, 4) && aligned_to(a.grad_obs, 4) &&
-                         aligned_to(a.log_alpha, 4) && aligned_to(a.log_beta, 4);
-  if (!vec && !narrow_ok) return SSNT_ERR_UNSUPPORTED;
-  const int Up = K * ((a.U + K - 1) / K);
-  const size_t head = stream_head_bytes(K, a.U, OBS);
-  if (head > kLdsBudget) return SSNT_ERR_UNSUPPORTED;
-  const size_t rows = (size_t)a.T * (vec ? a.U : Up) * sizeof(xf);
-  const bool lds = head + rows <= kLdsBudget;
-  if (!lds && (a.workspace == nullptr || a.workspace_bytes < (size_t)a.B * rows))
+  // which buffer loads and stores take at any dword alignment (so also a sliced log_trans / grad)
+  const bool vec = (a.U % K == 0) && all_aligned(a, 16, 16, 16);
+  if (!vec && !all_aligned(a, 4, 4, 16)) return SSNT_ERR_UNSUPPORTED;
+  if (!p.lds && (a.workspace == nullptr || a.workspace_bytes < p.workspace_bytes))
     return SSNT_ERR_WORKSPACE;
   if (vec)
-    return lds ? launch_stream_kernel<K, OBS, true, NC, NH, false>(a, head + rows, st)
-               : launch_stream_kernel<K, OBS, false, NC, NH, false>(a, head, st);
-  return lds ? launch_stream_kernel<K, OBS, true, NC, NH, true>(a, head + rows, st)
-             : launch_stream_kernel<K, OBS, false, NC, NH, true>(a, head, st);
+    return p.lds ? launch_stream_kernel<K, OBS, true, NC, NH, false>(a, p.shm_bytes, st)
+                 : launch_stream_kernel<K, OBS, false, NC, NH, false>(a, p.shm_bytes, st);
+  return p.lds ? launch_stream_kernel<K, OBS, true, NC, NH, true>(a, p.shm_bytes, st)
+               : launch_stream_kernel<K, OBS, false, NC, NH, true>(a, p.shm_bytes, st);
 }
 
 template <bool OBS>
-int launch_stream_obs(const FwdBwdArgs& a, hipStream_t st) {
-  // wave mix per lane width: 16 waves (3 converters + 4 gradient waves per direction) while a
-  // wave fits 128 VGPRs (K <= 2); 10 waves for K >= 4 (168 VGPRs, no spills)
-  if (a.U <= 64) return launch_stream_k<1, OBS, 3, 4>(a, st);
-  if (a.U <= 128) return launch_stream_k<2, OBS, 3, 4>(a, st);
-  if (a.U <= 256) return launch_stream_k<4, OBS, 2, 2>(a, st);
-  // K = 8 (U <= 512, configs[4]): the two-wave kernel. The streaming kernel needs 4-slot rings to
-  // fit LDS there and then ran 2.2x slower (5.7 vs 2.6 ms at B=64 T=2000 U=400).
-  return SSNT_ERR_UNSUPPORTED;
+int launch_stream_obs(const FwdBwdArgs& a, const RowsPlan& p, hipStream_t st) {
+  // 16 waves (3 converters + 4 gradient waves per direction) while a wave fits 128 VGPRs (K <= 2); else 10
+  if (p.K == 1) return launch_stream_k<1, OBS, 3, 4>(a, p, st);
+  if (p.K == 2) return launch_stream_k<2, OBS, 3, 4>(a, p, st);
+  return launch_stream_k<4, OBS, 2, 2>(a, p, st);
 }
 
 }  // namespace
@@ -797,18 +769,31 @@ int diag_read(void* host, size_t bytes) {
 #endif
 }
 
-size_t stream_head_bytes(int K, int U, bool obs) {
+// the kernel's LDS carve, then the rows [T][Up], Up = U padded to whole lane slices
+RowsPlan stream_plan(int B, int T, int U, bool obs) {
+  RowsPlan p{};
+  // K = 8 (U <= 512): not taken; with the 4-slot rings that fit LDS there it ran 2.2x slower
+  const int K = lanes_for(U);
+  if (K < 1 || K > 4) return p;
   const int R = obs ? in_slots<true>() : in_slots<false>();
-  const int R2o = obs ? out_slots<true>() : out_slots<false>();
-  const int R2 = R2o < R ? R2o : R;
-  const size_t Up = (size_t)K * ((U + K - 1) / K);  // (= U when U % K == 0)
+  const int R2 = std::min(obs ? out_slots<true>() : out_slots<false>(), R);
+  const size_t Up = (size_t)K * ((U + K - 1) / K);
   const size_t slot = (Up * 16 + (obs ? Up * 8 : 0) + 15) & ~(size_t)15;
-  return kCtlBytes + (size_t)64 * K * sizeof(xf) + (size_t)64 * 16 * K + 2 * (size_t)R * slot +
-         2 * (size_t)R2 * Up * sizeof(xf);
+  const size_t head = kCtlBytes + (size_t)64 * K * sizeof(xf) + (size_t)64 * 16 * K + 2 * (size_t)R * slot +
+                      2 * (size_t)R2 * Up * sizeof(xf);
+  if (head > kLdsBudget) return p;
+  const size_t rows = (size_t)T * Up * sizeof(xf);
+  p.supported = true, p.K = K;
+  p.lds = head + rows <= kLdsBudget;
+  p.shm_bytes = p.lds ? head + rows : head;
+  p.workspace_bytes = p.lds ? 0 : (size_t)B * rows;
+  return p;
 }
 
 int launch_fwd_bwd_stream(const FwdBwdArgs& a, hipStream_t st) {
-  return a.log_obs ? launch_stream_obs<true>(a, st) : launch_stream_obs<false>(a, st);
+  const RowsPlan p = stream_plan(a.B, a.T, a.U, a.log_obs != nullptr);
+  if (!p.supported) return SSNT_ERR_UNSUPPORTED;
+  return a.log_obs ? launch_stream_obs<true>(a, p, st) : launch_stream_obs<false>(a, p, st);
 }
 
 }  // namespace ssnt

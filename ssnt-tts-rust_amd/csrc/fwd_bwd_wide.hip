@@ -99,24 +99,17 @@ __device__ __forceinline__ int gctr_ld(const int* p) {
       __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
-__device__ __forceinline__ int wctr_ld(const int* p) {
-  return __builtin_amdgcn_readfirstlane(
-      __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-}
 // a plain LDS store (the address space spelled out: a volatile or atomic store through a generic
 // pointer can become a flat store, whose completion the compiler then waits for with vmcnt(0))
 typedef __attribute__((address_space(3))) int lds_int;
 __device__ __forceinline__ void wctr_st(int* p, int v) {
   *reinterpret_cast<lds_int*>(reinterpret_cast<size_t>(p) & 0xffffffffu) = v;
 }
-// compiler-only barrier: LDS data and counter accesses stay in program order (a wave's DS
-// instructions execute in order, so "write data, then counter" publishes without a wait)
-__device__ __forceinline__ void wbar() { asm volatile("" ::: "memory"); }
 
 // spin until *p >= target (bounded; an expired bound sets kStatusTimeout and gives up)
 __device__ __forceinline__ void wait_ge(const int* p, int target, int* status) {
-  if (wctr_ld(p) >= target) return;
-  for (int n = 0; wctr_ld(p) < target; ++n) {
+  if (ctr_ld(p) >= target) return;
+  for (int n = 0; ctr_ld(p) < target; ++n) {
     if (n > kSpinMax) {
       if (status && (threadIdx.x & 63) == 0) atomicOr(status, kStatusTimeout);
       return;
@@ -404,7 +397,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * (kMaxNW / 2 + 1 + (CONV ? kMaxNW / 2 :
       // (the slots of this block held steps i0 - kRB ..; the downstream wave consumes in the
       // same kBS blocks, so cons >= i1 - kRB already means the whole block's slots are free)
       if (has_dn) wait_ge(&ctl.cons[dn], i1 - kRB, a.status);
-      wbar();
+      cbar();
       const xf* rd = &ctl.bnd[has_up ? up : 0][i0 % kRB];
 #pragma unroll
       for (int k = 0; k < kBS; ++k) {  // (stale values when there is no upstream: unused)
@@ -422,18 +415,18 @@ __global__ __launch_bounds__(SPLIT ? 64 * (kMaxNW / 2 + 1 + (CONV ? kMaxNW / 2 :
         int pe;
         if constexpr (CONV && k % kSub == 0) {
           wait_ge(&ctl.cprod[w], i0 + k + kSub, a.status);
-          wbar();
+          cbar();
 #pragma unroll
           for (int q = 0; q < kSub; ++q) fpre[q] = fring[w * kFR * 64 + ((i0 + k + q) % kFR) * 64 + lane];
         }
         step(i0 + k, Kc, bm[k], be[k], pm, pe, i0 + k < i1);
         wp[k * ws] = xf{pm, pe};
         if constexpr (CONV && k % kSub == kSub - 1) {
-          wbar();
+          cbar();
           wctr_st(&ctl.ccons[w], i0 + k + 1);
         }
       });
-      wbar();
+      cbar();
       if (has_dn) wctr_st(&ctl.prod[w], i1);
       if (has_up) wctr_st(&ctl.cons[w], i1);
     }
@@ -452,13 +445,13 @@ __global__ __launch_bounds__(SPLIT ? 64 * (kMaxNW / 2 + 1 + (CONV ? kMaxNW / 2 :
       for (int i0 = 0; i0 < n; i0 += kPB) {
         const int i1 = min(i0 + kPB, n);
         wait_ge(&ctl.prod[src], i1, a.status);
-        wbar();
+        cbar();
         f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f}, v2 = {0.0f, 0.0f, 0.0f, 0.0f};
         if (lane < kL) {
           v = *reinterpret_cast<const f32x4*>(&ctl.bnd[src][i0 % kRB + 4 * lane]);
           v2 = *reinterpret_cast<const f32x4*>(&ctl.bnd[src][i0 % kRB + 4 * lane + 2]);
         }
-        wbar();
+        cbar();
         wctr_st(&ctl.cons[kProxy], i1);  // (DS in order: the reads above are done first)
         if (lane < kL) {
           rbuf_st4(v, gr, (i0 + 4 * lane) * 8, 0, kSC1);
@@ -491,12 +484,12 @@ __global__ __launch_bounds__(SPLIT ? 64 * (kMaxNW / 2 + 1 + (CONV ? kMaxNW / 2 :
         // wave 0 has read the previous lap of every one of them (its counter moves in kBS blocks,
         // so i1 - kRB would free only the slots up to the next block boundary past it)
         wait_ge(&ctl.cons[0], i0 + kPB - kRB, a.status);
-        wbar();
+        cbar();
         if (lane < kL) {
           *reinterpret_cast<f32x4*>(&ctl.bnd[kProxy][i0 % kRB + 4 * lane]) = v;
           *reinterpret_cast<f32x4*>(&ctl.bnd[kProxy][i0 % kRB + 4 * lane + 2]) = v2;
         }
-        wbar();
+        cbar();
         wctr_st(&ctl.prod[kProxy], i1);
       }
     }
@@ -515,7 +508,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * (kMaxNW / 2 + 1 + (CONV ? kMaxNW / 2 :
         constexpr int k = decltype(Kc)::value;
         if constexpr (k % kSub == 0) {
           wait_ge(&ctl.ccons[cw], i0 + k + kSub - kFR, a.status);
-          wbar();
+          cbar();
         }
         XRow<K> E, Sh, O;
         convert2(cr[k], E, Sh, O);
@@ -523,7 +516,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * (kMaxNW / 2 + 1 + (CONV ? kMaxNW / 2 :
         fr[((i0 + k) % kFR) * 64 + lane] = f32x4{E.m[0], __builtin_bit_cast(float, E.e[0]), Sh.m[0],
                                                  __builtin_bit_cast(float, Sh.e[0])};
         if constexpr (k % kSub == kSub - 1) {
-          wbar();
+          cbar();
           wctr_st(&ctl.cprod[cw], i0 + k + 1);
         }
       });
@@ -633,11 +626,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * (kMaxNW / 2 + 1 + (CONV ? kMaxNW / 2 :
       // ---------------- alpha[0..M]: rows 0..M of the workspace ----------------
       // alpha[0]: 1 at p = 0 (x obs[0][0]). Selects, not conditional stores: the row must stay
       // in registers (a partially written aggregate ends up in memory)
-      xf a0{0.5f, 1};
-      if constexpr (OBS) {
-        const xf o = xf_exp(lo[0], true);
-        a0 = xf_norm(o.m, o.e);
-      }
+      const xf a0 = alpha0<OBS>(lo);
       const bool first = seg == 0 && lane == 0;
       XRow<K> X;  // alpha row of this lane's K positions
       X.m[0] = first ? a0.m : 0.0f;
@@ -712,7 +701,8 @@ __global__ __launch_bounds__(SPLIT ? 64 * (kMaxNW / 2 + 1 + (CONV ? kMaxNW / 2 :
     return;
   } else {
     // ---------------- phase 2: Z at the cut (every workgroup, the oracle's tree) ----------------
-    // segment sums (in-lane levels of the tree, pairs (2i, 2i+1) first, then across lanes), then
+    // segment sums (in-lane levels of the tree, pairs (2i, 2i+1) first, then across lanes: the
+    // lines of fwd_bwd.hip and fwd_bwd_stream.hip, the three kept in step by hand), then
     // across segments; the waves of this workgroup cover all NW segments between them
     const int nwaves = __builtin_amdgcn_readfirstlane(blockDim.x >> 6);
     for (int sg = w; sg < NW; sg += nwaves) {
@@ -774,13 +764,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * (kMaxNW / 2 + 1 + (CONV ? kMaxNW / 2 :
       if (dir == 0 && part == 0 && threadIdx.x == 0) a.loss[b] = inf_loss;
       return;
     }
-    if (dir == 0 && part == 0 && threadIdx.x == 0) {
-      a.loss[b] = 0.0f - xf_log(Z);
-      if (a.z_state) {
-        a.z_state[2 * b] = Z.m;
-        a.z_state[2 * b + 1] = __builtin_bit_cast(float, Z.e);
-      }
-    }
+    if (dir == 0 && part == 0 && threadIdx.x == 0) publish_z<false>(a, b, Z, inf_loss);
     if (!comp) {
       if (proxy) run_proxy(dir == 0 ? S - M : M);
       return;
@@ -1026,10 +1010,7 @@ size_t fwd_bwd_wide_workspace_bytes(int B, int T, int U) {
 int launch_fwd_bwd_wide(const FwdBwdArgs& a, hipStream_t st, bool any_u) {
   if ((!any_u && a.U <= 256) || a.U > 64 * 2 * kMaxNW) return SSNT_ERR_UNSUPPORTED;
   // 8-byte granules: every tensor base must be 8-byte aligned (4 for the f32-element ones)
-  if (!aligned_to(a.log_trans, 8) || !aligned_to(a.grad, 8) || !aligned_to(a.workspace, 8) ||
-      !aligned_to(a.log_obs, 4) || !aligned_to(a.grad_obs, 4) || !aligned_to(a.log_alpha, 4) ||
-      !aligned_to(a.log_beta, 4))
-    return SSNT_ERR_UNSUPPORTED;
+  if (!all_aligned(a, 8, 4, 8)) return SSNT_ERR_UNSUPPORTED;
   if (!a.workspace || a.workspace_bytes < fwd_bwd_wide_workspace_bytes(a.B, a.T, a.U))
     return SSNT_ERR_WORKSPACE;
   // one descriptor per utterance tensor, position offsets up to 2^31 (row helpers)

@@ -1,6 +1,7 @@
-// lattice_dev.h -- device building blocks shared by the lattice forward-backward kernels
-// (fwd_bwd.hip: two-wave kernel; fwd_bwd_stream.hip: streaming kernel). Split-exponent
-// arithmetic itself is in xf_math.h.
+// lattice_dev.h -- device building blocks shared by the three lattice forward-backward kernels
+// (fwd_bwd_stream.hip: streaming; fwd_bwd_wide.hip: segmented; fwd_bwd.hip: two-wave fallback):
+// row moves, exp() of a row, the alpha / beta steps, and two pieces of the arithmetic contract
+//  as functions: alpha0 (all three), publish_z (streaming and segmented).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +32,12 @@ __device__ __forceinline__ float shl1(float x) {
 __device__ __forceinline__ int shl1(int x) {
   return __builtin_amdgcn_update_dpp(XF_EZERO, x, 0x130, 0xf, 0xf, false);
 }
+// LDS counter read (wave-uniform) and the compiler-only barrier that keeps LDS data and counter
+// accesses in program order (a wave's DS instructions execute in order: no wait to publish)
+__device__ __forceinline__ int ctr_ld(const int* p) {
+  return __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+}
+__device__ __forceinline__ void cbar() { asm volatile("" ::: "memory"); }
 
 template <int K, bool OBS>
 struct Item {
@@ -345,6 +352,16 @@ __device__ __forceinline__ void entering(const XRow<K>& Bn, const XRow<K>& O, XR
   }
 }
 
+// alpha[0][0]: 1 (x obs[0][0])
+template <bool OBS>
+__device__ __forceinline__ xf alpha0(const float* lo) {
+  if constexpr (OBS) {
+    const xf o = xf_exp(lo[0], true);
+    return xf_norm(o.m, o.e);
+  } else {
+    return xf{0.5f, 1};
+  }
+}
 template <int K>
 __device__ __forceinline__ void beta_step(XRow<K>& Bt, const XRow<K>& E, const XRow<K>& Sh,
                                           const XRow<K>& Q, const XRow<K>& R) {
@@ -414,6 +431,18 @@ __device__ __forceinline__ void publish_loss(const FwdBwdArgs& a, int b, float v
     __hip_atomic_store(sum_granule(a, b),
                        ((unsigned long long)tag << 32) | __builtin_bit_cast(unsigned, v),
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// one lane, Z formed: loss[b] = -ln Z (inf_loss when Z = 0: no path) -- SUM: through publish_loss,
+// for the kernel that sums inside the launch -- and Z itself for the float64 debug pass (ZS)
+template <bool SUM, bool ZS = true>
+__device__ __forceinline__ void publish_z(const FwdBwdArgs& a, int b, xf Z, float inf_loss, unsigned tag = 0u) {
+  const float v = (Z.m == 0.0f) ? inf_loss : 0.0f - xf_log(Z);
+  if constexpr (SUM) publish_loss(a, b, v, tag);
+  else a.loss[b] = v;
+  if (ZS && a.z_state) {
+    a.z_state[2 * b] = Z.m;
+    a.z_state[2 * b + 1] = __builtin_bit_cast(float, Z.e);
+  }
 }
 // one wave of workgroup 0: wait for every granule of this launch, write the sum, advance epoch
 __device__ __forceinline__ void finish_loss_sum(const FwdBwdArgs& a, unsigned tag) {

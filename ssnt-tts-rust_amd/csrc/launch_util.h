@@ -4,12 +4,20 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ssnt_internal.h"
 #include "ssnt_tts_c.h"
 
 namespace ssnt {
 
 // p is a multiple of m (a power of two); null counts as aligned
 inline bool aligned_to(const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & (m - 1)) == 0; }
+
+// fwd-bwd tensors aligned: log_trans / grad to `pair` bytes, the f32-element ones to `scalar`
+inline bool all_aligned(const FwdBwdArgs& a, uintptr_t pair, uintptr_t scalar, uintptr_t ws) {
+  return aligned_to(a.log_trans, pair) && aligned_to(a.grad, pair) && aligned_to(a.log_obs, scalar) &&
+         aligned_to(a.grad_obs, scalar) && aligned_to(a.log_alpha, scalar) &&
+         aligned_to(a.log_beta, scalar) && aligned_to(a.workspace, ws);
+}
 
 inline int launch_status() { return hipGetLastError() == hipSuccess ? SSNT_OK : SSNT_ERR_HIP; }
 

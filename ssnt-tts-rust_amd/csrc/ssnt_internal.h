@@ -1,4 +1,4 @@
-// ssnt_internal.h -- launchers shared between the kernels (fwd_bwd.hip, decode.hip) and the
+// ssnt_internal.h -- launchers shared between the kernel files (fwd_bwd_*.hip, decode.hip) and the
 // C-ABI host layer (capi.hip). Not part of the public interface (that is include/ssnt_tts_c.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,7 +19,7 @@ constexpr int kStatusRingTag = 1 << 5;           // diagnostic builds only: a ri
 
 int status_bits_to_code(int bits);
 
-// ---- lattice forward-backward (fwd_bwd.hip) ----
+// ---- lattice forward-backward (fwd_bwd_dispatch.hip: entry, kernel choice, workspace) ----
 struct FwdBwdArgs {
   const float* log_trans;  // (B,T,U,2)
   const float* log_obs;    // (B,T,U) or null
@@ -51,13 +51,24 @@ int launch_fwd_bwd_debug64(const FwdBwdArgs& a, double* loss64, double* log_alph
                            double* log_beta64, hipStream_t stream);
 size_t fwd_bwd_sum_state_bytes(int B);  // 64 + 8 B
 int launch_fwd_bwd(const FwdBwdArgs& a, hipStream_t stream);
+// positions per lane of the one-wave-per-row kernels: 1, 2, 4, 8 up to U = 64, 128, 256, 512; else 0
+inline int lanes_for(int U) { return U <= 64 ? 1 : U <= 128 ? 2 : U <= 256 ? 4 : U <= 512 ? 8 : 0; }
+// What a rows-in-LDS-or-workspace kernel decides from the shape alone (launcher and query share it)
+struct RowsPlan {
+  bool supported, lds;  // the kernel takes this shape; its rows fit LDS (else: the workspace)
+  int K;                // positions per lane
+  size_t shm_bytes, workspace_bytes;  // dynamic LDS of the launch; rows in the workspace (0 when lds)
+};
+RowsPlan stream_plan(int B, int T, int U, bool obs);  // fwd_bwd_stream.hip (rows padded to whole lane slices)
+RowsPlan simple_plan(int T, int U);  // fwd_bwd.hip (workspace_bytes unset: the query's size)
 // streaming kernel (fwd_bwd_stream.hip): SSNT_ERR_UNSUPPORTED for shapes it does not take
 int launch_fwd_bwd_stream(const FwdBwdArgs& a, hipStream_t stream);
+// two-wave fallback (fwd_bwd.hip): U <= 512, any alignment; writes loss[] only (no loss_sum)
+int launch_fwd_bwd_simple(const FwdBwdArgs& a, hipStream_t stream);
 // segmented kernel (fwd_bwd_wide.hip): long rows (256 < U <= 1024), or any U <= 1024 when
 // any_u; SSNT_ERR_UNSUPPORTED for other shapes
 int launch_fwd_bwd_wide(const FwdBwdArgs& a, hipStream_t stream, bool any_u);
 size_t fwd_bwd_wide_workspace_bytes(int B, int T, int U);
-size_t stream_head_bytes(int K, int U, bool obs);  // LDS bytes besides the lattice rows
 // Process-wide A/B knobs and the kernels only they reach: the A/B build (-DSSNT_AB, `make
 // lib-ab`, lib/ab/libssnt_tts_c_ab.so; tests and tools) only. The product dispatches by shape.
 #ifdef SSNT_AB

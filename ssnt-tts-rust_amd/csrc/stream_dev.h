@@ -1,7 +1,7 @@
 // stream_dev.h -- device building blocks of the role-pipelined streaming lattice kernel
-// (fwd_bwd_stream.hip): LDS counters and bounded spins, wave roles, the one-step chain
-// recurrences in split-exponent form, LDS row moves and the lane-slice global accesses. Included
-// inside namespace ssnt::{anonymous}.
+// (fwd_bwd_stream.hip): LDS counters (ctr_ld, cbar: lattice_dev.h) and bounded spins, wave
+// roles, the one-step chain recurrences in split-exponent form, LDS row moves and the lane-slice
+// global accesses. Included inside namespace ssnt::{anonymous}.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -56,9 +56,6 @@ __device__ __forceinline__ void tag_check(const int* t, int want, int* status) {
 constexpr int kTagFault = SSNT_DIAG_TAG_FAULT;
 #endif
 
-__device__ __forceinline__ int ctr_ld(const int* p) {
-  return __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-}
 __device__ __forceinline__ int ctr_acq(const int* p) {
   return __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
 }
@@ -68,9 +65,6 @@ __device__ __forceinline__ void ctr_st(int* p, int v) {
 __device__ __forceinline__ void ctr_rel(int* p, int v) {
   __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-// compiler-only barrier: keeps LDS data accesses and counter accesses in program order (the
-// hardware then executes them in that order)
-__device__ __forceinline__ void cbar() { asm volatile("" ::: "memory"); }
 
 // Diagnostic build only (-DSSNT_DIAG, `make lib-diag`): per-wave s_memtime totals, read back
 // with ssnt_diag_read() (tools/diag_fwd_bwd.py). g_diag[b][wave][8]: 0 total cycles, 1 cycles
@@ -142,10 +136,8 @@ __device__ __forceinline__ int first_missing(const int* cnt, int begin) {
 
 // Wave roles: chains, converters, gradient waves, in wave order. The hardware places wave w of
 // a workgroup on SIMD (base + w) % 4 (measured, tools/micro/micro_simd.hip), so this order
-// spreads each role over all four SIMDs. (Tried: giving each chain a SIMD shared only with
-// gradient waves -- idle until the cut -- and packing the converters onto the other two SIMDs:
-// the chains ran no faster and the packed converters starved them, 44 -> 48 us. kSimdRoles.)
-constexpr bool kSimdRoles = false;
+// spreads each role over all four SIMDs. (Chains on SIMDs shared only with gradient waves, the
+// converters packed onto the other two, starved the chains: 44 -> 48 us; retired to git history.)
 struct Role {
   int kind;  // 0 chain, 1 converter, 2 gradient wave
   int d;     // direction: 0 forward, 1 backward
@@ -154,25 +146,10 @@ struct Role {
 };
 template <int kNC, int kNH>
 __device__ __forceinline__ Role role_of(int w) {
-  constexpr int kW = 2 + 2 * kNC + 2 * kNH;
-  constexpr int n0 = (kW + 3) / 4, n1 = (kW + 2) / 4, n2 = (kW + 1) / 4, n3 = kW / 4;
-  constexpr bool simd_aware = kSimdRoles && n2 >= kNC && n3 >= kNC &&
-                              (n0 - 1) + (n2 - kNC) == kNH && (n1 - 1) + (n3 - kNC) == kNH;
   Role r;
-  if constexpr (simd_aware) {
-    const int g = w & 3, k = w >> 2;
-    if (g <= 1) {
-      r = k == 0 ? Role{0, g, 0, 0} : Role{2, g, k - 1, 0};
-    } else if (k < kNC) {
-      r = Role{1, g - 2, k, 0};
-    } else {
-      r = Role{2, g - 2, (g == 2 ? n0 - 1 : n1 - 1) + (k - kNC), 0};
-    }
-  } else {
-    if (w < 2) r = Role{0, w, 0, 0};
-    else if (w < 2 + 2 * kNC) r = Role{1, (w - 2) & 1, (w - 2) >> 1, 0};
-    else r = Role{2, (w - 2 - 2 * kNC) & 1, (w - 2 - 2 * kNC) >> 1, 0};
-  }
+  if (w < 2) r = Role{0, w, 0, 0};
+  else if (w < 2 + 2 * kNC) r = Role{1, (w - 2) & 1, (w - 2) >> 1, 0};
+  else r = Role{2, (w - 2 - 2 * kNC) & 1, (w - 2 - 2 * kNC) >> 1, 0};
   r.slot = r.kind == 0 ? r.d : r.kind == 1 ? 2 + 2 * r.idx + r.d : 2 + 2 * kNC + 2 * r.idx + r.d;
   return r;
 }
@@ -309,7 +286,6 @@ __device__ __forceinline__ void gst(const float* v, __amdgpu_buffer_rsrc_t r, in
     buf_st<F * K>(v, r, p0 * 4 * F);
   }
 }
-
 
 }  // namespace
 }  // namespace ssnt

@@ -526,6 +526,51 @@ def test_lds_edge_rows_without_workspace_query_mismatch(gpu, oracle, U, obs):
     _assert_bit_exact(g, o, ["loss", "grad"] + (["grad_obs"] if obs else []))
 
 
+@pytest.mark.parametrize("U", [63, 64, 127, 128, 255, 256])
+def test_workspace_query_matches_dispatch_at_lds_boundary(gpu, oracle, kernel_variant, U):
+    # The workspace query and the launchers share one shape plan: the query answers 0 up to some
+    # T* and a size from T* + 1 on, and on either side of that boundary every form a call can
+    # bring -- with / without log_obs, log_trans and grad 16-byte aligned (vector form) or offset
+    # by one float (narrow form, rows padded to whole lane slices) -- runs with exactly what the
+    # query gave (no workspace at T*, that many bytes at T* + 1) and is bit-exact. The sweep starts
+    # at T = 1, not 40: the wide K = 4 rings leave room for few rows, so at U = 255 / 256 the
+    # boundary lies below 40 (the query puts it at T* = 28; at U = 64 at 268), and the sweep has to
+    # bracket it for every U. No constant of the library is read: T* is whatever the query says.
+    if kernel_variant != 0:
+        pytest.skip("the LDS boundary is the default dispatch's (the forced kernels always get the workspace)")
+    dev = torch.device("cuda:0")
+    lib, B = gpu.load(), 2
+    sizes = {T: int(lib.ssnt_fwd_bwd_workspace_size(B, T, U)) for T in range(1, 331)}
+    zero = [T for T, n in sizes.items() if n == 0]
+    assert zero and len(zero) < len(sizes), "the range must bracket the LDS boundary"
+    Ts = max(zero)
+    assert all((n == 0) == (T <= Ts) for T, n in sizes.items()), "0 up to T*, non-zero beyond"
+    for T in (Ts, Ts + 1):
+        lt = oracle.synth_log_trans(B, T, U, seed=U + T)
+        lo = (np.random.default_rng(U + T).standard_normal((B, T, U)) * 15 - 40).astype(np.float32)
+        S, P = [T, T - 9], [min(U, T), min(U, T - 9) - 5]  # one full utterance, one with S < T, P < U
+        for obs in (False, True):
+            o = oracle.fwd_bwd_xf(lt, S, P, log_obs=lo if obs else None)
+            for shift in (0, 1):
+                flat = torch.zeros(lt.size + 4, dtype=torch.float32, device=dev)
+                x = flat[shift:shift + lt.size].view(B, T, U, 2)
+                x.copy_(torch.from_numpy(lt))
+                assert x.data_ptr() % 16 == 4 * shift
+                gv = torch.empty(lt.size + 4, dtype=torch.float32, device=dev)[shift:shift + lt.size].view(B, T, U, 2)
+                # (the wrapper passes no workspace when the query says 0, else exactly that size;
+                # check=True raises on any status but SSNT_OK)
+                r = gpu.ssnt_fwd_bwd(x, torch.tensor(S, dtype=torch.int32, device=dev),
+                                     torch.tensor(P, dtype=torch.int32, device=dev),
+                                     torch.from_numpy(lo).to(dev) if obs else None, check=True,
+                                     out={"grad": gv})
+                k = gpu.last_fwd_bwd_kernel()
+                assert k.startswith("k_fwd_bwd_stream<"), k
+                assert T > Ts or "LDS=1" in k, k  # (past T* a form with the smaller rings may still fit)
+                assert not shift or "NV=1" in k, k  # (odd U runs the narrow form at any alignment)
+                g = {n: v.cpu().numpy() for n, v in r.items() if n != "status"}
+                _assert_bit_exact(g, o, ["loss", "grad"] + (["grad_obs"] if obs else []))
+
+
 _C3 = {}
 
 
