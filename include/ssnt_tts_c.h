@@ -211,6 +211,32 @@ int ssnt_v2_fwd_bwd_device(const float *logits, const int *duration_table, const
                            float *log_alpha, float *log_beta, void *workspace,
                            size_t workspace_bytes, int *status, void *stream);
 
+/* ---- exact best duration path (Viterbi) on the v2 duration-class lattice.
+ * The max-plus recurrence over F4's lattice (same inputs, states, windows and class rule as
+ * ssnt_v2_fwd_bwd_device): IEEE f32 adds and strict compares, classes in increasing order (a tie
+ * keeps the lower class; the final total is the lowest among equal maxima), so the outputs are
+ * bit-identical to a plain f32 restatement. log_prob (B) = log-probability of the most probable
+ * admissible class sequence; duration_class (B,T) = its class at every step (-1 for steps >=
+ * I_b); duration (B,T) = duration_table[class] (0 for steps >= I_b); total (B) = its final total
+ * (= O_b in band mode). Each of the three may be NULL. An utterance with no admissible path (I_b
+ * = 0, band mode with O_b > max_total, log_prob = -inf, a length outside the tensor, which also
+ * sets SSNT_ERR_BAD_LENGTH in `status`, or a negative duration, which sets SSNT_ERR_BAD_INDEX)
+ * gets log_prob -inf, classes -1, durations 0 and total -1. -inf logits are legal; +inf is not
+ * clamped. Limits as F4: duration_class_size > 64 and a row beyond LDS return
+ * SSNT_ERR_UNSUPPORTED, max_total outside [0, 1<<24] SSNT_ERR_INVALID_ARG. `workspace` holds
+ * ssnt_v2_viterbi_align_workspace_size() bytes: 0 (NULL workspace) while the backpointer bytes
+ * of one utterance fit LDS; with duration_class and duration both NULL no backpointers are kept
+ * and no workspace is needed. Device pointers, asynchronous on `stream`. New: the reference only
+ * searches this lattice with a pruned beam. */
+size_t ssnt_v2_viterbi_align_workspace_size(int batch, int max_steps, int max_total, bool test_mode);
+int ssnt_v2_viterbi_align_device(const float *logits, const int *duration_table,
+                                 const int *input_length, const int *output_length, int batch,
+                                 int max_steps, int duration_class_size, int max_total,
+                                 int zero_duration_id, bool allow_skip, bool test_mode,
+                                 float *log_prob, int *duration_class, int *duration, int *total,
+                                 void *workspace, size_t workspace_bytes, int *status,
+                                 void *stream);
+
 /* ---- batched decode steps, device pointers (the reference FFI fixes v1 to B=1,
  * ssnt_tts_c/src/lib.rs:13; its Rust API takes B, src/lib.rs:121). max_beam_width = beam_width
  * as in every reference call site (ssnt_tts_c/src/lib.rs:82,217,342). ---- */

@@ -120,9 +120,29 @@ struct V2FwdBwdArgs {
   int chunk;                 // set by the launcher
   int* status;
 };
-size_t v2_fwd_bwd_wcap(int max_total, bool test_mode);
 size_t v2_fwd_bwd_workspace_bytes(int B, int Imax, int max_total, bool test_mode);
 int launch_v2_fwd_bwd(const V2FwdBwdArgs& a, hipStream_t stream);
+
+// ---- exact best duration path on the v2 lattice (v2_viterbi.hip) ----
+struct V2ViterbiArgs {
+  const float* logits;       // (B, Imax, D) per-step class log-probs
+  const int* table;          // (D) duration_table, >= 0
+  const int* input_length;   // (B) I_b <= Imax
+  const int* output_length;  // (B) O_b
+  int B, Imax, D, X;         // X = max_total + 1 totals per row
+  int zid;                   // zero_duration_id
+  bool allow_skip, test_mode;
+  float* log_prob;           // (B)
+  int* duration_class;       // (B, Imax) or null
+  int* duration;             // (B, Imax) or null
+  int* total;                // (B) or null
+  void* workspace;           // backpointer bytes when they do not fit LDS
+  size_t workspace_bytes;
+  int Wcap;                  // set by the launcher
+  int* status;
+};
+size_t v2_viterbi_workspace_bytes(int B, int Imax, int max_total, bool test_mode);
+int launch_v2_viterbi(const V2ViterbiArgs& a, hipStream_t stream);
 
 // ---- beam-search decode (decode.hip) ----
 enum class Variant : int { V1 = 0, V2 = 1, Tone = 2 };

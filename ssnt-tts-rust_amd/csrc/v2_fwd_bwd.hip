@@ -31,56 +31,13 @@
 #include "buffer_ops.h"
 #include "launch_util.h"
 #include "ssnt_internal.h"
+#include "v2_lattice_dev.h"
 #include "xf_math.h"
 
 namespace ssnt {
 namespace {
 
 constexpr int kF4Threads = 512;
-
-__device__ __forceinline__ int f4_f2i(float x) {  // Rust `f32 as i32` (saturating, NaN -> 0)
-  if (x != x) return 0;
-  if (x >= 2147483648.0f) return 2147483647;
-  if (x <= -2147483648.0f) return (-2147483647 - 1);
-  return (int)x;
-}
-
-struct F4Utt {
-  int I, O, X, dmax;
-  bool test;
-};
-
-// cells of row r that can hold mass: [lo, hi] (empty when lo > hi); = oracle f4_window
-__device__ __forceinline__ void f4_window(const F4Utt& u, int r, int& lo, int& hi) {
-  if (r == 0) {
-    lo = 0;
-    hi = 0;
-    return;
-  }
-  if (u.test) {
-    const long long h = (long long)r * u.dmax;
-    lo = 0;
-    hi = h < u.X - 1 ? (int)h : u.X - 1;
-    return;
-  }
-  const int t = r - 1;
-  if ((long long)(u.I - (t + 1)) * 3 > u.O) {  // will_overrun (src/v2.rs:106-111)
-    lo = 1;
-    hi = 0;
-    return;
-  }
-  const float diagonal = (float)u.O / (float)u.I * (float)(t + 1);  // src/v2.rs:94-104
-  const float upper_range = (float)u.O * 0.1f;
-  const float lower_range = (float)u.O * 0.05f;
-  int lb = f4_f2i(fmaxf(diagonal - lower_range, 0.0f));
-  int ub = f4_f2i(fminf(diagonal + upper_range, (float)u.O));
-  if (t == u.I - 1) {  // src/v2.rs:135-137
-    lb = max(lb, u.O);
-    ub = min(ub, u.O);
-  }
-  lo = max(lb, 0);
-  hi = min(ub, u.X - 1);
-}
 
 // debug row: ln of the window cells, -inf elsewhere (row == nullptr: all -inf)
 __device__ __forceinline__ void f4_log_row(float* dst, const xf* row, int lo, int hi, int X) {
@@ -134,15 +91,6 @@ __device__ __forceinline__ xf f4_cell(int xr, const int (&dk)[DC], const xf* w, 
     for (int i = 0; i < len / 2; ++i) m[i] = m[2 * i] + m[2 * i + 1];
   }
   return xf_norm(m[0], em);
-}
-
-// workgroup barrier ordering LDS only: __syncthreads() would also wait for every global store
-// in flight (vmcnt(0)), i.e. one HBM write round trip per sweep step; nothing in these kernels
-// reads back global memory written in the same launch
-__device__ __forceinline__ void lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
 template <int CTRL>
@@ -212,29 +160,6 @@ __device__ __forceinline__ int f4_reduce_classes(xf (&acc)[N], int lane, int cls
   }
 }
 
-// per-utterance state both kernels derive the same way; false: no lattice (loss written by
-// the forward sweep, every output row zero / -inf)
-__device__ __forceinline__ bool f4_setup(const V2FwdBwdArgs& a, int b, const int* dur, F4Utt& u,
-                                         bool report) {
-  u.I = a.input_length[b];
-  u.O = a.output_length[b];
-  u.X = a.X;
-  u.test = a.test_mode;
-  u.dmax = 0;
-  bool neg = false;
-  for (int i = 0; i < a.D; ++i) {
-    u.dmax = max(u.dmax, dur[i]);
-    neg |= dur[i] < 0;
-  }
-  const bool bad_len = u.I < 0 || u.I > a.Imax || u.O < 0;
-  if (report && (bad_len || neg) && threadIdx.x == 0 && a.status)
-    atomicOr(a.status, neg ? kStatusBadIndex : kStatusBadLength);
-  // band mode with O > max_total: the final total can never equal O (src/v2.rs:135-137), so the
-  // lattice is empty (= oracle f4_one); its windows could also exceed the band-sized Wcap
-  const bool beyond = !u.test && u.O > u.X - 1;
-  return !(bad_len || neg || u.I == 0 || beyond);
-}
-
 // workspace: alpha rows [B][Imax+1][Wc] | beta rows [B][Imax+1][Wc] | Z [B]
 struct F4Ws {
   xf *alpha, *beta, *z;
@@ -245,7 +170,6 @@ __device__ __forceinline__ F4Ws f4_ws(const V2FwdBwdArgs& a) {
   return F4Ws{base, base + rows, base + 2 * rows};
 }
 
-constexpr int kF4Pad = 64;  // zero cells either side of a row window (PADDED: dmax <= kF4Pad)
 // sweep steps per staged chunk of class weights
 template <int DC>
 constexpr int f4_chunk() { return DC <= 32 ? 64 : 32; }
@@ -573,13 +497,6 @@ __global__ __launch_bounds__(f4_grad_threads<DC>()) void k_f4_grad(V2FwdBwdArgs 
 }
 
 }  // namespace
-
-size_t v2_fwd_bwd_wcap(int max_total, bool test_mode) {
-  const int X = max_total + 1;
-  if (test_mode) return (size_t)X;
-  const size_t band = (size_t)(0.15 * (double)max_total) + 8;  // ub - lb + 1 <= 0.15 O + 3
-  return band < (size_t)X ? band : (size_t)X;
-}
 
 size_t v2_fwd_bwd_workspace_bytes(int B, int Imax, int max_total, bool test_mode) {
   if (B <= 0 || Imax <= 0 || max_total < 0) return 0;

@@ -29,7 +29,8 @@ __all__ = [
     "levenshtein_edit_distance", "ssnt_fwd_bwd", "ssnt_viterbi_align", "SSNTLatticeLoss",
     "ssnt_lattice_loss",
     "lattice_beam_search_decode", "v2_lattice_beam_search_decode",
-    "tone_latent_lattice_beam_search_decode", "v2_fwd_bwd", "V2DurationLoss", "v2_duration_loss",
+    "tone_latent_lattice_beam_search_decode", "v2_fwd_bwd", "v2_viterbi_align", "V2DurationLoss",
+    "v2_duration_loss",
     "SsntError", "FLAG_TERMINAL_EMIT", "FLAG_ZERO_INFINITY",
 ]
 
@@ -498,6 +499,54 @@ def v2_fwd_bwd(logits, duration_table, input_length, output_length, zero_duratio
     if debug:
         res["log_alpha"] = la
         res["log_beta"] = lb
+    return res
+
+
+def v2_viterbi_align(logits, duration_table, input_length, output_length, zero_duration_id, *,
+                     allow_skip=False, test_mode=False, max_total=None, need_path=True,
+                     check=False, out=None):
+    """Exact best duration path (Viterbi) on the v2 duration-class lattice.
+
+    Inputs as ``v2_fwd_bwd`` (``max_total`` defaults to max(output_length), read back from the
+    device). Returns a dict with ``log_prob`` (B,) f32, the log-probability of the most probable
+    class sequence the v2 move rules admit; ``duration_class`` (B,T) i32, its class at every step
+    (-1 for steps >= I_b); ``duration`` (B,T) i32 = duration_table[class] (0 for steps >= I_b);
+    ``total`` (B,) i32, its final total (= O_b in band mode); ``status``. An utterance without an
+    admissible path gets -inf, -1, 0 and -1. A tie keeps the lower class (and the lower final
+    total). ``need_path=False`` computes ``log_prob`` only. ``out`` may pass preallocated
+    tensors under the same keys."""
+    lib = load(require_gpu=True)
+    lg = _dev(logits, torch.float32, "logits")
+    dev = lg.device
+    B, T, D = lg.shape
+    table = _dev(duration_table, torch.int32, "duration_table").reshape(D)
+    il = _dev(input_length, torch.int32, "input_length").reshape(B)
+    ol = _dev(output_length, torch.int32, "output_length").reshape(B)
+    if max_total is None:
+        max_total = int(ol.max().item()) if B > 0 else 0
+    out = dict(out or {})
+    lp = _buf(out, dev, "log_prob", (B,), torch.float32)
+    cls = _buf(out, dev, "duration_class", (B, T), torch.int32, want=need_path)
+    dur = _buf(out, dev, "duration", (B, T), torch.int32, want=need_path)
+    tot = _buf(out, dev, "total", (B,), torch.int32, want=need_path)
+    wsb = int(lib.ssnt_v2_viterbi_align_workspace_size(B, T, int(max_total), bool(test_mode))) \
+        if need_path else 0
+    ws = _workspace(dev, wsb)
+    st = out.get("status")
+    if st is None:
+        st = _status(dev)
+    else:
+        st.zero_()
+    rc = lib.ssnt_v2_viterbi_align_device(_p(lg), _p(table), _p(il), _p(ol), B, T, D,
+                                          int(max_total), int(zero_duration_id), bool(allow_skip),
+                                          bool(test_mode), _p(lp), _p(cls), _p(dur), _p(tot),
+                                          _p(ws), wsb, _p(st), _stream(dev))
+    _finish("v2_viterbi_align", rc, st, check)
+    res = {"log_prob": lp, "status": st}
+    if need_path:
+        res["duration_class"] = cls
+        res["duration"] = dur
+        res["total"] = tot
     return res
 
 
