@@ -21,7 +21,23 @@
 // The cost model that shapes this (measured, tools/micro/): a lone wave issues one VALU
 // instruction per ~4.4 cycles whether or not the instructions depend on each other, so a chain
 // step costs its instruction count. The chains therefore carry only the recurrence; every
-// other instruction lives on another wave.
+// other instruction lives on another wave. That count includes the chain's counter polls, so
+// they are kept short (stream_dev.h: Ctl, first_missing). In the disassembly of the product
+// instance (K=2, no obs), per chain:
+//   step     23 instructions before the cut: 20 VALU (two of them the storage address: the
+//            compiler re-forms stride << 3 every step), 2 ds_read_b128 of factors, 1
+//            ds_write_b128 of the row; plus 2 s_waitcnt and one address add for the factors'
+//            second element block. (One VALU fewer with a precomputed byte stride: no gain
+//            measured)
+//   poll      8: address move, one ds_read_b128 of the direction's counters, s_waitcnt,
+//            v_min3_i32, s_nop, v_readfirstlane, s_cmp, branch. (22 when each counter was a
+//            count read with its own ds_read_b32 / s_waitcnt / v_readfirstlane and scaled to a
+//            row number with s_mul + s_add before the minimum; 28 with four counters.)
+//   publish   6: two ds_write_b32 (chain, sread). (5 as one ds_write_b64 of an adjacent pair:
+//            no gain measured)
+// Before the cut a chain polls the converters once per 4 steps; after it, the converters and
+// the gradient waves once per 2 steps: up to 5.5 instructions per step before, 25 after, with
+// the long polls, 2 and 8.5 with the short ones. Measured effect: DESIGN.md 5.1.
 //
 // Rows kept for the gradients: alpha[0..M] and beta[M+1..S-1] in "storage" (LDS when T*U*8 B
 // fits beside the rings, else a global workspace), beta[M] in a cut buffer; the chain rows past
@@ -154,7 +170,12 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
     }
   };
   // converted-input slot j of direction d: per position (E.m, E.e, X.m, X.e); obs block after
-  if (threadIdx.x < kCtlBytes / 4) reinterpret_cast<int*>(smem)[threadIdx.x] = 0;
+  // control block: zero, except the row counters, which start at their owner's first row
+  // (conv: w; help[0]: M + w; help[1]: S - M + w -- Ctl's first 4 * kMaxW words)
+  if (threadIdx.x < kCtlBytes / 4) {
+    const int t = threadIdx.x, w = t & (kMaxW - 1);
+    reinterpret_cast<int*>(smem)[t] = t < 2 * kMaxW ? w : t < 3 * kMaxW ? M + w : t < 4 * kMaxW ? S - M + w : 0;
+  }
   XRow<K> X = xrow_zero<K>();
   if (role.kind == 0 && role.d == 0) {  // alpha[0]: 1 at p = 0 (x obs[0][0])
     if (lane == 0) {
@@ -240,10 +261,18 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
       const int r = hb + h + kNH * i;  // bwd: beta[s] at stream row r
       return d == 0 ? r : r + 1;
     };
+    // The chain's progress also vouches for the factor slot: the chain has read row r's slot,
+    // so the converter has written it. Not so for the terminal transition (forward stream row
+    // S-1): the alpha chain ends at row S-2 and never reads that slot, so its gradient wave
+    // waits for the converters themselves (a late converter left the slot's previous row there:
+    // one wrong gradient cell, caught by the diagnostic build's ring tags).
+    auto unread_by_chain = [&](int i) { return d == 0 && hb + h + kNH * i == S - 1; };
     auto wait_chain = [&](int i) {
       const int need = need_of(i);
       if (chain_seen < need)
         chain_seen = spin_until<true>([&] { return ctr_ld(&ctl->chain[d]); }, need, a.status, dg);
+      if (unread_by_chain(i))
+        spin_until<true>([&] { return first_missing<kNC>(ctl->conv[0]); }, S, a.status, dg);
       cbar();
     };
     auto fetch = [&](int i, GIn& in) {
@@ -281,7 +310,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
       }
 #endif
       cbar();
-      ctr_st(&ctl->help[d][h], i + 1);  // ring rows read (in-order DS): reusable
+      ctr_st(&ctl->help[d][h], r + kNH);  // my next row; ring rows read (in-order DS): reusable
     };
     auto emit = [&](int i, const GIn& in) {
           const int s = row_of(i);
@@ -365,7 +394,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
     };
     auto row = [&](int i, GIn& cur, GIn& nxt) {
       const bool more = i + 1 < nmine;
-      const bool early = more && chain_seen >= need_of(i + 1);
+      const bool early = more && chain_seen >= need_of(i + 1) && !unread_by_chain(i + 1);
       if (early) fetch(i + 1, nxt);
       emit(i, cur);
       if (more && !early) {
@@ -448,7 +477,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
             if (seen_chain < need_c)
               seen_chain = spin_until<true>([&] { return ctr_ld(&ctl->sread[d]); }, need_c, a.status, dg);
             if (q >= hb && seen_grad <= q)
-              seen_grad = spin_until<true>([&] { return first_missing<kNH>(ctl->help[d], hb); }, q + 1, a.status, dg);
+              seen_grad = spin_until<true>([&] { return first_missing<kNH>(ctl->help[d]); }, q + 1, a.status, dg);
           }
           cbar();
 #ifdef SSNT_DIAG
@@ -477,7 +506,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
           tag_put(&ctl->ctag[d][r % R], r + kTagFault);
 #endif
           cbar();
-          ctr_st(&ctl->conv[d][c], k + 1);
+          ctr_st(&ctl->conv[d][c], r + kNC);  // my next row
 #ifdef SSNT_DIAG
           dg.ph[1] += dg.now() - tw0;
 #endif
@@ -502,15 +531,15 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
   // tried: no faster before the cut, slower after it -- less ring slack; so was issuing the
   // read of row r+3 into a dead buffer before the step's arithmetic, which does keep three reads
   // in flight in the .s: before the cut a step still costs ~300 cycles, so the LDS latency is
-  // not what bounds it; nor do the converter polls -- with them skipped (timing experiment) a
-  // step before the cut also takes ~300 cycles). All LDS
+  // not what bounds it; with the converter polls skipped (timing experiment) a step before the
+  // cut took ~274 cycles against 326: the polls' own instructions, see the header). All LDS
   // addresses are per-lane pointers prepared before the loop (lanes past U: junk / clamped).
   __builtin_amdgcn_s_setprio(3);
   const int d = role.d;
   int ready = 0;  // stream rows known converted
   auto wait_row = [&](int r) {  // r: a row that exists
     if (r >= ready)
-      ready = spin_until<false>([&] { return first_missing<kNC>(ctl->conv[d], 0); }, r + 1, a.status, dg);
+      ready = spin_until<false>([&] { return first_missing<kNC>(ctl->conv[d]); }, r + 1, a.status, dg);
   };
   const unsigned char* sptr[R];  // slot j, this lane's factors (element block 0)
 #pragma unroll
@@ -603,7 +632,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
       if (phase2) {
         const int q = r1 - kR2;  // newest previous occupant the half-block overwrites
         if (q > M && help_seen <= q)
-          help_seen = spin_until<false>([&] { return first_missing<kNH>(ctl->help[0], M); }, q + 1, a.status, dg);
+          help_seen = spin_until<false>([&] { return first_missing<kNH>(ctl->help[0]); }, q + 1, a.status, dg);
       }
       cbar();
     };
@@ -683,7 +712,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
         // previous occupants: stream rows up to r1-1-kR2, read by gradient rows q and q+1
         const int q = r1 - 1 - kR2;
         if (q > c && help_seen <= q + 1)
-          help_seen = spin_until<false>([&] { return first_missing<kNH>(ctl->help[1], S - M); }, q + 2, a.status, dg);
+          help_seen = spin_until<false>([&] { return first_missing<kNH>(ctl->help[1]); }, q + 2, a.status, dg);
       }
       cbar();
     };

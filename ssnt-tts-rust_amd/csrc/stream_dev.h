@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
+#include <stddef.h>
 
 #include <type_traits>
 #include <utility>
@@ -21,11 +22,16 @@ constexpr size_t kCtlBytes = 512;  // + the ring tags below
 constexpr size_t kCtlBytes = 256;
 #endif
 
-struct Ctl {
-  int conv[2][kMaxW];  // per direction / converter: rows of its share written to the ring
+// Counters hold stream row numbers, not counts: worker w of NW owns rows begin + w + NW*i and
+// publishes "the first row of my share that is not done" (begin + w before its first row; the
+// kernel writes these initial values with the zero fill, before the first barrier), so a reader
+// needs only the minimum over the workers (first_missing). The words of one direction lie in
+// one aligned 16-byte group and are read with one LDS access.
+struct alignas(16) Ctl {
+  int conv[2][kMaxW];  // per direction / converter: first row of its share not yet in the ring (begin 0)
+  int help[2][kMaxW];  // per direction / gradient wave: first row of its share not finished (begin M / S-M)
   int chain[2];        // per direction: stream rows the chain has finished (outputs written)
   int sread[2];        // per direction: stream rows whose ring slots the chain has read
-  int help[2][kMaxW];  // per direction / gradient wave: rows of its share finished
   int a_ready;       // alpha[0..M] stored
   int bm_ready;      // beta[M+1..S-1] stored, beta[M] in the cut buffer
   int z_ready;       // Z published
@@ -40,6 +46,10 @@ struct Ctl {
   int rtag[2][16];
 #endif
 };
+static_assert(offsetof(Ctl, conv) == 0 && offsetof(Ctl, help) == 2 * kMaxW * sizeof(int),
+              "the kernel's initial fill addresses conv / help by word index");
+static_assert(sizeof(int[kMaxW]) == 16 && offsetof(Ctl, conv) % 16 == 0 && offsetof(Ctl, help) % 16 == 0,
+              "one 16-byte LDS read per direction (first_missing)");
 static_assert(sizeof(Ctl) <= kCtlBytes, "control block");
 
 #ifdef SSNT_DIAG
@@ -125,13 +135,27 @@ __device__ __forceinline__ int spin_until(F f, int target, int* status, Diag& dg
   return v;
 }
 
-// workers w = 0..NW-1 own rows begin + w + NW*i; counter w = rows done. First row not done.
+// First stream row not done by workers 0..NW-1 (Ctl): one wide read of the direction's counters.
+// The words are stored independently by their owners and only grow, and each 32-bit word of the
+// read is whole, so a snapshot taken while they change can only report an earlier row. Volatile:
+// read again on every poll (through an explicit LDS pointer: a volatile access through a generic
+// pointer stays a flat instruction). Every lane reads the same address; the result is wave-uniform.
+typedef int ctr_v2 __attribute__((ext_vector_type(2)));
+typedef int ctr_v4 __attribute__((ext_vector_type(4)));
+#define SSNT_LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
 template <int NW>
-__device__ __forceinline__ int first_missing(const int* cnt, int begin) {
-  int m = INT_MAX;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) m = min(m, begin + w + NW * ctr_ld(cnt + w));
-  return m;
+__device__ __forceinline__ int first_missing(const int* cnt) {
+  static_assert(NW >= 2 && NW <= kMaxW, "2..4 workers per direction");
+  int m;
+  if constexpr (NW == 2) {
+    const ctr_v2 v = *SSNT_LDS_PTR(const volatile ctr_v2, cnt);
+    m = min(v.x, v.y);
+  } else {
+    const ctr_v4 v = *SSNT_LDS_PTR(const volatile ctr_v4, cnt);
+    m = min(min(v.x, v.y), v.z);
+    if constexpr (NW == 4) m = min(m, v.w);
+  }
+  return __builtin_amdgcn_readfirstlane(m);
 }
 
 // Wave roles: chains, converters, gradient waves, in wave order. The hardware places wave w of
