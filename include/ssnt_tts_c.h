@@ -192,6 +192,34 @@ int ssnt_viterbi_align_device(const float *log_trans, const float *log_obs, cons
                               float *log_prob, int *position, int *duration, void *workspace,
                               size_t workspace_bytes, int *status, void *stream);
 
+/* ---- alignments drawn from the posterior of the emit/shift lattice ----
+ * Forward filter, backward sample over the tensors of ssnt_fwd_bwd_device: the forward sweep is
+ * the forward-backward's alpha recurrence in split-exponent f32; walking back from (S_b-1, P_b-1),
+ * sample k moves from position p to p-1 at step s iff uniform[b,k,s] * t < m', where m' is the
+ * move term entering (s,p) and t the sum of its stay and move terms, both f32 at their common
+ * exponent (one multiply, one ordered compare). uniform (B, num_samples, T) is the caller's
+ * randomness: values are clamped to [0, 1 - 2^-24], NaN counts as 0, so every output is a valid
+ * monotone path for any input and the call is a pure function of its arguments (the library holds
+ * no generator state). With uniform i.i.d. on [0,1) a path is drawn with its posterior probability
+ * p(path | log_trans, log_obs), up to the f32 rounding of alpha. log_prob (B, num_samples) = the
+ * log-probability of each drawn path, summed in f32 along the path in the order of DESIGN.md 2.4
+ * (with the terminal emit under SSNT_FLAG_TERMINAL_EMIT, the only flag accepted); position
+ * (B, num_samples, T) and duration (B, num_samples, U) as ssnt_viterbi_align_device, per sample
+ * (NULL = skip). An infeasible utterance (S_b < P_b, S_b = 0, P_b = 0, alpha[S_b-1][P_b-1] = 0, or
+ * a length beyond the tensor, which also sets SSNT_ERR_BAD_LENGTH in `status`) gets log_prob
+ * -inf, positions -1 and durations 0 for every sample. -inf inputs are legal. max_pos > 1024
+ * returns SSNT_ERR_UNSUPPORTED, num_samples outside [1, 64] SSNT_ERR_INVALID_ARG. `workspace`
+ * holds ssnt_sample_align_workspace_size() bytes: 0 (NULL workspace) while the decision bits of
+ * one utterance (num_samples * T words per lane slot) fit LDS; the bits are needed for log_prob
+ * too, so the workspace does not depend on which outputs are requested. Device pointers,
+ * asynchronous on `stream`. New: the reference has no sampler. */
+size_t ssnt_sample_align_workspace_size(int batch, int max_steps, int max_pos, int num_samples);
+int ssnt_sample_align_device(const float *log_trans, const float *log_obs, const int *step_len,
+                             const int *pos_len, const float *uniform, int batch, int max_steps,
+                             int max_pos, int num_samples, int flags, float *log_prob,
+                             int *position, int *duration, void *workspace,
+                             size_t workspace_bytes, int *status, void *stream);
+
 /* ---- F4: v2 duration-class (semi-Markov) forward-backward (DESIGN.md
  * "Duration lattice"). New: the reference only decodes this lattice; the move rules are the v2
  * decode's (src/v2.rs:94-166 -- band, overrun, exact final total, zero-duration class; test_mode

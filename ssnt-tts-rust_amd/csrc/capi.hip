@@ -808,6 +808,25 @@ int ssnt_viterbi_align_device(const float* log_trans, const float* log_obs, cons
   return launch_viterbi(a, as_stream(stream));
 }
 
+size_t ssnt_sample_align_workspace_size(int batch, int max_steps, int max_pos, int num_samples) {
+  if (batch <= 0 || max_steps <= 0 || max_pos <= 0 || max_pos > 1024 || num_samples < 1 || num_samples > 64)
+    return 0;
+  return sample_align_workspace_bytes(batch, max_steps, max_pos, num_samples);
+}
+
+int ssnt_sample_align_device(const float* log_trans, const float* log_obs, const int* step_len,
+                             const int* pos_len, const float* uniform, int batch, int max_steps,
+                             int max_pos, int num_samples, int flags, float* log_prob,
+                             int* position, int* duration, void* workspace,
+                             size_t workspace_bytes, int* status, void* stream) {
+  SampleAlignArgs a{};
+  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
+  a.uniform = uniform; a.B = batch; a.T = max_steps; a.U = max_pos; a.NS = num_samples;
+  a.flags = flags; a.log_prob = log_prob; a.position = position; a.duration = duration;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  return launch_sample_align(a, as_stream(stream));
+}
+
 size_t ssnt_v2_fwd_bwd_workspace_size(int batch, int max_steps, int max_total, bool test_mode) {
   return v2_fwd_bwd_workspace_bytes(batch, max_steps, max_total, test_mode);
 }

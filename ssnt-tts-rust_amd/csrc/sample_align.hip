@@ -1,0 +1,527 @@
+// sample_align.hip -- alignments drawn from the posterior of the emit/shift lattice for gfx950.
+//
+// Semantics: DESIGN.md 2.4. Forward filter, backward sample: the forward sweep is the alpha
+// recurrence of the forward-backward in split-exponent ("xf") f32; for every cell it leaves, per
+// sample k, the bit "uniform[k][s] * t < m'" (m' = the move term entering the cell, t = stay +
+// move, both at their common exponent). The backward walk is the best-path kernel's backtrace
+// (viterbi.hip) over those bits, one walk per sample. One workgroup = one utterance, 5 waves:
+//
+//   wave 0      the chain: alpha[s][p] for s = 1..S-1. A lane holds K consecutive positions (p =
+//               K*lane + j, K = 1..16: one wave spans U <= 1024); the left neighbour of j = 0 is one
+//               DPP wave shift. Per sample and j one multiply and one compare; the compare's SGPR
+//               pair is the 64-bit decision word (bit `lane` of word j <-> position K*lane + j).
+//   waves 1..4  loaders: the rows of the next chunk (R rows) go global -> registers while the chain
+//               sweeps the current chunk, are converted there (exp() of the inputs as unnormalized
+//               xf, the clamp of the uniforms: nothing transcendental on the chain), then go to LDS
+//               transposed to [row][j][lane] as in viterbi.hip. Two LDS buffers, one workgroup
+//               barrier per chunk, range-checked buffer loads without predicates.
+//
+// Who takes the decisions (HELP, smp_help): as a rule the loader waves, a chunk behind the chain:
+// the chain leaves (t, m') of every cell in a third pair of LDS buffers, loader wave w decides the
+// rows w, w+4, ... of the previous chunk between issuing its loads and committing them (it alone
+// loads and reads those rows' uniforms, so the barrier per chunk is all the ordering needed). For
+// one sample on a long row (K >= 8) the chain wave decides itself (measured).
+//
+// Decision words: NS*T*K*8 bytes per utterance, laid out [sample][step][j], in LDS when they fit
+// beside the chunk buffers, else in the caller's workspace (ordinary vector stores by the deciding
+// wave; read back for the walks in blocks through the chunk buffers, which are free by then).
+//
+// Walks, same launch: sample k belongs to wave k mod 5. Each wave walks by runs (64 lanes test the
+// bit of the current position at 64 consecutive steps, one ballot finds the step that entered it),
+// fills its own start[] and writes duration / position from it, then sums the path's log-probability
+// sequentially in f32: 64 lanes gather 64 steps' terms, one lane order adds them.
+#include <hip/hip_runtime.h>
+
+#include <utility>
+
+#include "lattice_dev.h"
+#include "launch_util.h"
+
+namespace ssnt {
+namespace {
+
+constexpr int kSmpLoaders = 4;                        // loader waves
+constexpr int kSmpWaves = 1 + kSmpLoaders;
+constexpr int kSmpThreads = 64 * kSmpWaves;
+constexpr int kSmpUnits = 16;                         // positions per loader lane and chunk
+constexpr int kSmpMaxRpw = 8;                         // rows per loader wave and chunk, at most
+constexpr int kSmpMaxR = kSmpLoaders * kSmpMaxRpw;    // rows per chunk, at most
+constexpr int kSmpMaxSamples = 64;
+constexpr int kSmpUUnits = kSmpMaxR * kSmpMaxSamples / (64 * kSmpLoaders);  // uniforms per loader lane and chunk
+constexpr int kSmpUStride = kSmpMaxSamples + 1;       // floats per row of the uniform buffer (padded)
+constexpr int kSmpJunk = 64;                          // elements behind each buffer: unused units' writes
+constexpr size_t kSmpHeadBytes = 64;
+constexpr int kSmpNoUnit = 0x7fffffff;                // byte offset no buffer range contains
+constexpr float kSmpUMax = 0x1.fffffep-1f;            // 1 - 2^-24
+
+extern "C" __device__ int smp_writelane(int v, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
+
+struct SmpShared {
+  int feasible;
+};
+
+constexpr int smp_k(int U) { return U <= 64 ? 1 : U <= 128 ? 2 : U <= 256 ? 4 : U <= 512 ? 8 : 16; }
+constexpr int smp_kstride(int K) { return 64 + (K > 1 ? 32 / K : 0); }
+// Who takes the decisions (measured): the loader waves, a chunk behind the chain,
+// from (t, m') rows the chain leaves in LDS -- except one sample on a long row (K >= 8), where the
+// chain wave takes them itself.
+inline bool smp_help(int U, int NS) { return !(NS == 1 && smp_k(U) >= 8); }
+inline int smp_chunk_rows(int U) {
+  int r = kSmpUnits / ((U + 63) / 64);
+  r = r < 1 ? 1 : r > kSmpMaxRpw ? kSmpMaxRpw : r;
+  return kSmpLoaders * r;
+}
+struct SmpLayout {
+  int K, R;
+  bool help;
+  size_t start_off, lt_off, ob_off, u_off, tm_off, bits_off, total;  // bytes
+};
+// lds_bits: the decision words of the utterance in LDS (else: the workspace, no LDS of their own)
+inline SmpLayout smp_layout(int T, int U, int R, int NS, bool obs, bool lds_bits) {
+  SmpLayout L{};
+  L.K = smp_k(U);
+  L.R = R;
+  L.help = smp_help(U, NS);
+  const size_t buf = (size_t)R * L.K * smp_kstride(L.K) + kSmpJunk;  // elements of one buffer
+  const size_t ubuf = (size_t)R * kSmpUStride + kSmpJunk;
+  L.start_off = kSmpHeadBytes;
+  L.lt_off = (L.start_off + (size_t)kSmpWaves * (U + 2) * 4 + 15) & ~(size_t)15;
+  L.ob_off = L.lt_off + 2 * buf * 16;
+  L.u_off = L.ob_off + (obs ? 2 * buf * 8 : 0);
+  L.tm_off = L.u_off + 2 * ubuf * 4;
+  L.bits_off = L.tm_off + (L.help ? 2 * (size_t)R * L.K * 64 * 8 : 0);  // two chunks of (t, m') rows
+  L.total = L.bits_off + (lds_bits ? (size_t)NS * T * L.K * 8 : 0);
+  return L;
+}
+// the deepest chunk the unit count gives, shortened until everything fits LDS
+inline SmpLayout smp_pick(int T, int U, int NS, bool obs, bool lds_bits) {
+  int R = smp_chunk_rows(U);
+  SmpLayout L = smp_layout(T, U, R, NS, obs, lds_bits);
+  while (L.total > kLdsBudget && R > 1) {
+    R = R > kSmpLoaders ? R - kSmpLoaders : R / 2;
+    L = smp_layout(T, U, R, NS, obs, lds_bits);
+  }
+  return L;
+}
+// The decision words stay in LDS when they fit beside the chunk buffers the log_obs form has in
+// workspace mode (from the shape alone: the query does not know whether log_obs is given).
+inline bool smp_bits_fit(int T, int U, int NS) {
+  const int R = smp_pick(T, U, NS, true, false).R;
+  return smp_layout(T, U, R, NS, true, true).total <= kLdsBudget;
+}
+
+struct SmpParams {
+  int R;
+  unsigned start_off, lt_off, ob_off, u_off, tm_off, bits_off;
+};
+
+// WS: the decision words live in the workspace (else in LDS); HELP: the loader waves decide
+template <int K, bool OBS, bool WS, bool HELP>
+__global__ __launch_bounds__(kSmpThreads) void k_sample_align(SampleAlignArgs a, SmpParams q) {
+  constexpr int kKs = smp_kstride(K);
+  constexpr int kRow = K * kKs;  // LDS row stride in cells
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63;
+  const int T = a.T, U = a.U, R = q.R, NS = a.NS;
+  const int S = a.step_len[b];
+  const int P = a.pos_len[b];
+  const size_t TU = (size_t)T * U;
+  const float* lt = a.log_trans + (size_t)b * TU * 2;
+  const float* lo = OBS ? a.log_obs + (size_t)b * TU : nullptr;
+  const float* un = a.uniform + (size_t)b * NS * T;
+  float* lp_out = a.log_prob + (size_t)b * NS;
+  int* pos_out = a.position ? a.position + (size_t)b * NS * T : nullptr;
+  int* dur_out = a.duration ? a.duration + (size_t)b * NS * U : nullptr;
+  const float ninf = -__builtin_inff();
+
+  SmpShared* sh = reinterpret_cast<SmpShared*>(smem);
+  int* startb = reinterpret_cast<int*>(smem + q.start_off);
+  float4* ltb = reinterpret_cast<float4*>(smem + q.lt_off);
+  float2* obb = reinterpret_cast<float2*>(smem + q.ob_off);
+  float* ubb = reinterpret_cast<float*>(smem + q.u_off);
+  float2* tmb = reinterpret_cast<float2*>(smem + q.tm_off);
+  const int bufsz = R * kRow + kSmpJunk;       // cells of one buffer
+  const int ubufsz = R * kSmpUStride + kSmpJunk;
+  unsigned long long* bits = WS ? reinterpret_cast<unsigned long long*>(a.workspace) + (size_t)b * NS * T * K
+                                : reinterpret_cast<unsigned long long*>(smem + q.bits_off);
+
+  auto fill_empty = [&]() {  // the infeasible rule, every sample
+    for (int k = tid; k < NS; k += kSmpThreads) lp_out[k] = ninf;
+    if (pos_out)
+      for (int s = tid; s < NS * T; s += kSmpThreads) pos_out[s] = -1;
+    if (dur_out)
+      for (int p = tid; p < NS * U; p += kSmpThreads) dur_out[p] = 0;
+  };
+  if (!(S >= 1 && P >= 1 && S <= T && P <= U && S >= P)) {
+    if ((S > T || P > U || S < 0 || P < 0) && a.status && tid == 0) atomicOr(a.status, kStatusBadLength);
+    fill_empty();
+    return;
+  }
+
+  // ------------------------------------------------------------------ loaders: chunk geometry
+  // Loader wave w takes rows w, w+4, ... of a chunk; its lanes stride across a row, one position
+  // per unit. goff = byte offset from the chunk's first row (kSmpNoUnit for a unit outside the
+  // geometry: its load is out of every range), loff = LDS cell in the buffer (the junk behind it
+  // for such a unit). The uniforms of a chunk: row i of sample k at ugoff, to uloff = [i][k].
+  const int NC = (S - 1 + R - 1) / R;  // chunks of transition rows 0..S-2
+  int goff[kSmpUnits], loff[kSmpUnits], ugoff[kSmpUUnits], uloff[kSmpUUnits];
+  f32x2 lreg[kSmpUnits];
+  float oreg[OBS ? kSmpUnits : 1], ureg[kSmpUUnits];
+  const bool loader = wave >= 1;
+  if (loader) {
+    const int w = wave - 1;
+    const int upr = (U + 63) / 64;  // units per row and lane
+    static_for<kSmpUnits>([&](auto Ic) __attribute__((always_inline)) {
+      constexpr int u = decltype(Ic)::value;
+      const int row = w + kSmpLoaders * (u / upr);
+      const int p = lane + 64 * (u % upr);
+      const bool ok = row < R && p < U;
+      goff[u] = ok ? (row * U + p) * 8 : kSmpNoUnit;
+      loff[u] = ok ? row * kRow + (p % K) * kKs + p / K : R * kRow + lane;
+    });
+    static_for<kSmpUUnits>([&](auto Ic) __attribute__((always_inline)) {
+      constexpr int u = decltype(Ic)::value;
+      const int f = u * 64 + lane;  // this wave's rows w, w+4, ... only: it alone reads them back
+      const int i = w + kSmpLoaders * (f % kSmpMaxRpw), k = f / kSmpMaxRpw;
+      const bool ok = i < R && k < NS;
+      ugoff[u] = ok ? (k * T + i) * 4 : kSmpNoUnit;
+      uloff[u] = ok ? i * kSmpUStride + k : R * kSmpUStride + lane;
+    });
+  }
+  // global -> registers: transition rows [c*R, min(c*R + R, S-1)); log_obs and uniforms of the
+  // rows they lead to, [c*R + 1, ...)
+  auto issue = [&](int c) __attribute__((always_inline)) {
+    const int r0 = c * R;
+    const int n = min(R, S - 1 - r0);
+    const __amdgpu_buffer_rsrc_t rs = brsrc(lt + (size_t)r0 * U * 2, (unsigned)(n * U) * 8u);
+    static_for<kSmpUnits>([&](auto Ic) __attribute__((always_inline)) {
+      constexpr int u = decltype(Ic)::value;
+      lreg[u] = rbuf_ld2(rs, goff[u], 0, 0);
+    });
+    if constexpr (OBS) {
+      const __amdgpu_buffer_rsrc_t ro = brsrc(lo + (size_t)(r0 + 1) * U, (unsigned)(n * U) * 4u);
+      static_for<kSmpUnits>([&](auto Ic) __attribute__((always_inline)) {
+        constexpr int u = decltype(Ic)::value;
+        oreg[u] = rbuf_ld1(ro, goff[u] == kSmpNoUnit ? kSmpNoUnit : goff[u] >> 1, 0, 0);
+      });
+    }
+    // the range ends with row r0 + n of the last sample (r0 + n <= S - 1 < T: inside the tensor)
+    const __amdgpu_buffer_rsrc_t ru = brsrc(un + r0 + 1, (unsigned)((NS - 1) * T + n) * 4u);
+    static_for<kSmpUUnits>([&](auto Ic) __attribute__((always_inline)) {
+      constexpr int u = decltype(Ic)::value;
+      ureg[u] = rbuf_ld1(ru, ugoff[u], 0, 0);
+    });
+  };
+  // registers -> LDS buffer c & 1, converted: (E.m, E.e, Sh.m, Sh.e) per cell, (O.m, O.e), and the
+  // clamped uniforms (NaN -> 0)
+  auto commit = [&](int c) __attribute__((always_inline)) {
+    float4* dst = ltb + (size_t)(c & 1) * bufsz;
+    static_for<kSmpUnits>([&](auto Ic) __attribute__((always_inline)) {
+      constexpr int u = decltype(Ic)::value;
+      float me, ms;
+      int ee, es;
+      xf_exp_pair(lreg[u].x, lreg[u].y, true, true, me, ee, ms, es);
+      dst[loff[u]] = make_float4(me, __builtin_bit_cast(float, ee), ms, __builtin_bit_cast(float, es));
+    });
+    if constexpr (OBS) {
+      float2* dsto = obb + (size_t)(c & 1) * bufsz;
+      static_for<kSmpUnits>([&](auto Ic) __attribute__((always_inline)) {
+        constexpr int u = decltype(Ic)::value;
+        const xf o = xf_exp(oreg[u], true);
+        dsto[loff[u]] = make_float2(o.m, __builtin_bit_cast(float, o.e));
+      });
+    }
+    float* dstu = ubb + (size_t)(c & 1) * ubufsz;
+    static_for<kSmpUUnits>([&](auto Ic) __attribute__((always_inline)) {
+      constexpr int u = decltype(Ic)::value;
+      float x = ureg[u];
+      x = x >= 0.0f ? x : 0.0f;
+      dstu[uloff[u]] = fminf(x, kSmpUMax);
+    });
+  };
+
+  // ------------------------------------------------------------------ sweep
+  float Am[K];
+  int Ae[K];
+  int mlo = 0, mhi = 0;  // lane j < K: the low / high half of the decision word j in flight
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    Am[j] = 0.0f;
+    Ae[j] = XF_EZERO;
+  }
+  if (wave == 0 && lane == 0) {
+    const xf a0 = alpha0<OBS>(lo);
+    Am[0] = a0.m;
+    Ae[0] = a0.e;
+  }
+  // the decisions of step s (row s of every sample's words) from the aligned terms of its cells
+  // and the row's uniforms (lane k: sample k)
+  auto decide = [&](const float* tt, const float* mp, float urow, int s) __attribute__((always_inline)) {
+    unsigned long long* dst = bits + (size_t)s * K;
+    for (int k = 0; k < NS; ++k) {
+      const float uk = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, urow), k));
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        const bool mv = uk * tt[j] < mp[j];
+        const unsigned long long w = __ballot(mv);
+        mlo = smp_writelane((int)(unsigned)w, j, mlo);
+        mhi = smp_writelane((int)(unsigned)(w >> 32), j, mhi);
+      }
+      const unsigned long long myw = ((unsigned long long)(unsigned)mhi << 32) | (unsigned)mlo;
+      if (lane < K) dst[(size_t)k * T * K + lane] = myw;
+    }
+  };
+  // helper form: loader wave w decides rows w, w+4, ... of chunk c from the chain's (t, m') rows
+  auto help = [&](int c) __attribute__((always_inline)) {
+    const int r0 = c * R;
+    const int n = min(R, S - 1 - r0);
+    const float2* TM = tmb + (size_t)(c & 1) * R * K * 64 + lane;
+    const float* UB = ubb + (size_t)(c & 1) * ubufsz + lane;
+    for (int i = wave - 1; i < n; i += kSmpLoaders) {
+      float tt[K], mp[K];
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        const float2 v = TM[(i * K + j) * 64];
+        tt[j] = v.x;
+        mp[j] = v.y;
+      }
+      decide(tt, mp, UB[i * kSmpUStride], r0 + i + 1);
+    }
+  };
+  if (loader && NC > 0) {
+    issue(0);
+    commit(0);
+  }
+  __syncthreads();
+  for (int c = 0; c < NC; ++c) {
+    if (loader && c + 1 < NC) issue(c + 1);
+    if (HELP && loader && c > 0) help(c - 1);
+    if (wave == 0) {
+      const int r0 = c * R;
+      const int n = min(R, S - 1 - r0);
+      const float4* Bf = ltb + (size_t)(c & 1) * bufsz + lane;
+      const float2* OB = obb + (size_t)(c & 1) * bufsz + lane;
+      const float* UB = ubb + (size_t)(c & 1) * ubufsz + lane;
+      struct Row {
+        float4 t[K];
+        float2 o[OBS ? K : 1];
+        float u;
+      };
+      auto ld = [&](Row& r, int i) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          r.t[j] = Bf[i * kRow + j * kKs];
+          if constexpr (OBS) r.o[j] = OB[i * kRow + j * kKs];
+        }
+        r.u = HELP ? 0.0f : UB[i * kSmpUStride];
+      };
+      // alpha[s] from alpha[s-1] and transition row s-1 (the operations of alpha_step,
+      // lattice_dev.h, with the two aligned terms kept for the decisions)
+      auto step = [&](const Row& r, int s) __attribute__((always_inline)) {
+        float sm[K], hm[K], tt[K], mp[K];
+        int se[K], he[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          sm[j] = Am[j] * r.t[j].x;
+          se[j] = Ae[j] + __builtin_bit_cast(int, r.t[j].y);
+          hm[j] = Am[j] * r.t[j].z;
+          he[j] = Ae[j] + __builtin_bit_cast(int, r.t[j].w);
+        }
+        const float lm = shr1(hm[K - 1]);
+        const int le = shr1(he[K - 1]);
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          const float xm = (j == 0) ? lm : hm[j > 0 ? j - 1 : 0];
+          const int xe = (j == 0) ? le : he[j > 0 ? j - 1 : 0];
+          const int em = max(se[j], xe);
+          mp[j] = xldexp(xm, xe - em);
+          tt[j] = xldexp(sm[j], se[j] - em) + mp[j];
+          float sum = tt[j];
+          int ee = em;
+          if constexpr (OBS) {
+            sum = sum * r.o[j].x;
+            ee = ee + __builtin_bit_cast(int, r.o[j].y);
+          }
+          const xf nv = xf_norm(sum, ee);
+          Am[j] = nv.m;
+          Ae[j] = nv.e;
+        }
+        if constexpr (HELP) {  // the terms of row i of this chunk, for the helpers
+          float2* TM = tmb + (size_t)(c & 1) * R * K * 64 + lane;
+#pragma unroll
+          for (int j = 0; j < K; ++j) TM[((s - 1 - r0) * K + j) * 64] = make_float2(tt[j], mp[j]);
+        } else {
+          decide(tt, mp, r.u, s);
+        }
+      };
+      Row ra, rb;
+      ld(ra, 0);
+      int i = 0;
+      for (; i + 1 < n; i += 2) {
+        ld(rb, i + 1);
+        step(ra, r0 + i + 1);
+        ld(ra, min(i + 2, n - 1));
+        step(rb, r0 + i + 2);
+      }
+      if (i < n) step(ra, r0 + i + 1);
+    }
+    if (loader && c + 1 < NC) commit(c + 1);
+    __syncthreads();
+  }
+
+  // ------------------------------------------------------------------ feasibility
+  if (wave == 0) {
+    float v = 0.0f;
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+      if (K * lane + j == P - 1) v = Am[j];
+    if (K * lane <= P - 1 && P - 1 < K * lane + K) sh->feasible = v != 0.0f;  // the one lane that holds P-1
+  } else if (HELP && NC > 0) {
+    help(NC - 1);  // the last chunk's decisions
+  }
+  if constexpr (WS) __threadfence();  // the stored words, before the other waves read them
+  __syncthreads();
+  if (!sh->feasible) {
+    fill_empty();
+    return;
+  }
+
+  // ------------------------------------------------------------------ one walk per sample
+  int* start = startb + wave * (U + 2);
+  // workspace mode: this wave's share of the chunk buffers holds walk_rows rows of one sample
+  const int region = (4 * bufsz / kSmpWaves) / K * K;  // 8-byte words (a cell of the buffer is two)
+  unsigned long long* wbuf = reinterpret_cast<unsigned long long*>(ltb) + (size_t)wave * region;
+  const int walk_rows = region / K;
+  auto pos_of = [&](int s) {  // the last p with start[p] <= s (start[0] = 0, increasing)
+    int lo_p = 0, hi_p = P - 1;
+    while (lo_p < hi_p) {
+      const int mid = (lo_p + hi_p + 1) >> 1;
+      if (start[mid] <= s) lo_p = mid; else hi_p = mid - 1;
+    }
+    return lo_p;
+  };
+  for (int k = wave; k < NS; k += kSmpWaves) {
+    cbar();
+    for (int p = lane; p < P; p += 64) start[p] = 0;
+    if (lane == 0) start[P] = S;
+    const unsigned long long* kb = bits + (size_t)k * T * K;
+    int s = S - 1, p = P - 1;
+    while (p > 0 && s >= 1) {
+      int lo_row = 0;
+      const unsigned long long* wb = kb;
+      if constexpr (WS) {  // rows [lo_row, s] of the sample -> this wave's LDS
+        lo_row = max(1, s - walk_rows + 1);
+        const unsigned long long* src = kb + (size_t)lo_row * K;
+        const int nw = (s - lo_row + 1) * K;
+        cbar();
+        for (int j0 = lane; j0 < nw; j0 += 8 * 64) {  // 8 loads in flight per lane
+          unsigned long long t[8];
+#pragma unroll
+          for (int i = 0; i < 8; ++i)
+            t[i] = __hip_atomic_load(src + min(j0 + i * 64, nw - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+          for (int i = 0; i < 8; ++i)
+            if (j0 + i * 64 < nw) wbuf[j0 + i * 64] = t[i];
+        }
+        cbar();
+        wb = wbuf;
+      }
+      const int first = max(lo_row, 1);
+      while (p > 0 && s >= first) {
+        const int ss = s - lane;
+        int bit = 0;
+        if (ss >= first) bit = (int)((wb[(size_t)(ss - lo_row) * K + (p & (K - 1))] >> (p / K)) & 1ull);
+        const unsigned long long m = __ballot(bit != 0);
+        if (m == 0) {
+          s = max(s - 64, first - 1);
+        } else {  // the nearest step below s that entered p
+          const int st = s - (__ffsll((long long)m) - 1);
+          if (lane == 0) start[p] = st;
+          s = st - 1;
+          p = p - 1;
+        }
+      }
+    }
+    cbar();
+    if (dur_out)
+      for (int pp = lane; pp < U; pp += 64) dur_out[(size_t)k * U + pp] = pp < P ? start[pp + 1] - start[pp] : 0;
+    if (pos_out)
+      for (int ss = lane; ss < T; ss += 64) pos_out[(size_t)k * T + ss] = ss < S ? pos_of(ss) : -1;
+    // log_prob: the sequential f32 sum of DESIGN.md 2.4, 64 steps' terms gathered at a time
+    float v = OBS ? lo[0] : 0.0f;
+    for (int s0 = 0; s0 < S - 1; s0 += 64) {
+      const int ss = s0 + lane;
+      float x = 0.0f, y = 0.0f;
+      if (ss < S - 1) {
+        const int p0 = pos_of(ss), p1 = pos_of(ss + 1);
+        x = lt[((size_t)ss * U + p0) * 2 + (p1 - p0)];
+        if constexpr (OBS) y = lo[(size_t)(ss + 1) * U + p1];
+      }
+      const int n = min(64, S - 1 - s0);
+      for (int i = 0; i < n; ++i) {
+        v = v + __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), i));
+        if constexpr (OBS)
+          v = v + __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, y), i));
+      }
+    }
+    if (a.flags & SSNT_FLAG_TERMINAL_EMIT) v = v + lt[((size_t)(S - 1) * U + (P - 1)) * 2];
+    if (lane == 0) lp_out[k] = v;
+  }
+}
+
+template <int K, bool OBS, bool WS>
+int launch_sample_k(const SampleAlignArgs& a, const SmpLayout& L, hipStream_t st) {
+  SmpParams q{};
+  q.R = L.R;
+  q.start_off = (unsigned)L.start_off; q.lt_off = (unsigned)L.lt_off; q.ob_off = (unsigned)L.ob_off;
+  q.u_off = (unsigned)L.u_off; q.tm_off = (unsigned)L.tm_off; q.bits_off = (unsigned)L.bits_off;
+  if (L.help)
+    return launch_lds(k_sample_align<K, OBS, WS, true>, dim3(a.B), dim3(kSmpThreads), L.total, kLdsBudget, st, a, q);
+  return launch_lds(k_sample_align<K, OBS, WS, false>, dim3(a.B), dim3(kSmpThreads), L.total, kLdsBudget, st, a, q);
+}
+
+template <bool OBS, bool WS>
+int launch_sample_obs(const SampleAlignArgs& a, const SmpLayout& L, hipStream_t st) {
+  switch (L.K) {
+    case 1: return launch_sample_k<1, OBS, WS>(a, L, st);
+    case 2: return launch_sample_k<2, OBS, WS>(a, L, st);
+    case 4: return launch_sample_k<4, OBS, WS>(a, L, st);
+    case 8: return launch_sample_k<8, OBS, WS>(a, L, st);
+    default: return launch_sample_k<16, OBS, WS>(a, L, st);
+  }
+}
+
+}  // namespace
+
+size_t sample_align_workspace_bytes(int B, int T, int U, int NS) {
+  if (smp_bits_fit(T, U, NS)) return 0;
+  return (size_t)B * NS * T * smp_k(U) * 8;
+}
+
+int launch_sample_align(const SampleAlignArgs& a, hipStream_t st) {
+  if (a.B < 0 || a.T < 0 || a.U < 0 || (a.flags & ~SSNT_FLAG_TERMINAL_EMIT)) return SSNT_ERR_INVALID_ARG;
+  if (a.NS < 1 || a.NS > kSmpMaxSamples) return SSNT_ERR_INVALID_ARG;
+  if (a.B == 0) return SSNT_OK;
+  if (!a.log_trans || !a.step_len || !a.pos_len || !a.uniform || !a.log_prob) return SSNT_ERR_INVALID_ARG;
+  if (a.U > 1024) return SSNT_ERR_UNSUPPORTED;
+  if (!aligned_to(a.log_trans, 8) || !aligned_to(a.log_obs, 4) || !aligned_to(a.uniform, 4))
+    return SSNT_ERR_UNSUPPORTED;
+  // the byte offsets of the range-checked loads are 32-bit
+  if ((size_t)a.NS * a.T * 4 >= (size_t)kSmpNoUnit) return SSNT_ERR_UNSUPPORTED;
+  const bool obs = a.log_obs != nullptr;
+  const int U = a.U > 0 ? a.U : 1;  // (T == 0 or U == 0: every utterance is infeasible)
+  const bool fit = a.T == 0 || a.U == 0 || smp_bits_fit(a.T, U, a.NS);
+  if (!fit) {
+    const size_t need = sample_align_workspace_bytes(a.B, a.T, a.U, a.NS);
+    if (!a.workspace || a.workspace_bytes < need || !aligned_to(a.workspace, 8)) return SSNT_ERR_WORKSPACE;
+  }
+  const SmpLayout L = smp_pick(a.T, U, a.NS, obs, fit);
+  if (L.total > kLdsBudget) return SSNT_ERR_UNSUPPORTED;
+  if (fit) return obs ? launch_sample_obs<true, false>(a, L, st) : launch_sample_obs<false, false>(a, L, st);
+  return obs ? launch_sample_obs<true, true>(a, L, st) : launch_sample_obs<false, true>(a, L, st);
+}
+
+}  // namespace ssnt

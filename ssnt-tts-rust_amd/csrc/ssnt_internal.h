@@ -100,6 +100,24 @@ struct ViterbiArgs {
 size_t viterbi_workspace_bytes(int B, int T, int U);
 int launch_viterbi(const ViterbiArgs& a, hipStream_t stream);
 
+// ---- alignments drawn from the posterior of the emit/shift lattice (sample_align.hip) ----
+struct SampleAlignArgs {
+  const float* log_trans;  // (B,T,U,2)
+  const float* log_obs;    // (B,T,U) or null
+  const int* step_len;     // (B)
+  const int* pos_len;      // (B)
+  const float* uniform;    // (B,NS,T): the random input, one number per sample and step
+  int B, T, U, NS, flags;  // NS: samples per utterance, 1..64
+  float* log_prob;   // (B,NS)
+  int* position;     // (B,NS,T) or null
+  int* duration;     // (B,NS,U) or null
+  void* workspace;   // decision bits when they do not fit LDS
+  size_t workspace_bytes;
+  int* status;
+};
+size_t sample_align_workspace_bytes(int B, int T, int U, int NS);
+int launch_sample_align(const SampleAlignArgs& a, hipStream_t stream);
+
 // ---- F4: v2 duration-class forward-backward (v2_fwd_bwd.hip) ----
 struct V2FwdBwdArgs {
   const float* logits;       // (B, Imax, D) per-step class log-probs

@@ -5,8 +5,8 @@ The function names, argument order and meaning mirror the reference's Python op 
 130), over torch device tensors instead of TF graph tensors. Every call goes through the C ABI
 of ``lib/libssnt_tts_c.so`` (include/ssnt_tts_c.h) on torch's current HIP stream; there is no CPU
 fallback. Added beside them: the lattice forward-backward (``ssnt_fwd_bwd``,
-``SSNTLatticeLoss``), the exact best path over the same lattice (``ssnt_viterbi_align``) and a
-fused multi-step decode (``lattice_beam_search_decode``).
+``SSNTLatticeLoss``), the exact best path over the same lattice (``ssnt_viterbi_align``),
+alignments drawn from its posterior (``ssnt_sample_align``) and a fused multi-step decode (``lattice_beam_search_decode``).
 
 Errors the reference raises by panicking (v2 "no candidate", upsample duration mismatch,
 out-of-range branch) are raised here as ``SsntError`` when ``check=True`` (the default), which
@@ -26,7 +26,8 @@ FLAG_ZERO_INFINITY = 2
 __all__ = [
     "beam_search_decode", "extract_best_beam_branch", "ssnt_tts_v2_beam_search_decode",
     "order_beam_branch", "upsample_source_indexes", "tone_latent_beam_search_decode",
-    "levenshtein_edit_distance", "ssnt_fwd_bwd", "ssnt_viterbi_align", "SSNTLatticeLoss",
+    "levenshtein_edit_distance", "ssnt_fwd_bwd", "ssnt_viterbi_align", "ssnt_sample_align",
+    "SSNTLatticeLoss",
     "ssnt_lattice_loss",
     "lattice_beam_search_decode", "v2_lattice_beam_search_decode",
     "tone_latent_lattice_beam_search_decode", "v2_fwd_bwd", "v2_viterbi_align", "V2DurationLoss",
@@ -418,6 +419,50 @@ def ssnt_viterbi_align(log_trans, step_len, pos_len, log_obs=None, *, terminal_e
                                        _p(pos), _p(dur), _p(ws), wsb, _p(st), _stream(dev))
     _finish("ssnt_viterbi_align", rc, st, check)
     res = {"log_prob": lp, "status": st}
+    if need_path:
+        res["position"] = pos
+        res["duration"] = dur
+    return res
+
+
+def ssnt_sample_align(log_trans, step_len, pos_len, num_samples, log_obs=None, *, uniform=None,
+                      generator=None, terminal_emit=True, need_path=True, out=None, check=True):
+    """Alignments drawn from the posterior of the emit/shift lattice.
+
+    Inputs as ``ssnt_fwd_bwd``; ``num_samples`` K in [1, 64] paths per utterance. ``uniform``
+    (B,K,T) f32 is the randomness, one number per sample and step (clamped to [0, 1 - 2^-24], NaN
+    counts as 0); without it ``torch.rand((B,K,T), generator=generator)`` is drawn on the device.
+    The call is a pure function of its tensors. Returns a dict with ``log_prob`` (B,K) f32, the
+    log-probability of each drawn path; ``position`` (B,K,T) i32 and ``duration`` (B,K,U) i32 as
+    ``ssnt_viterbi_align``, per sample; ``uniform``, the numbers used; ``status``. An infeasible
+    utterance gets -inf, -1 and 0 for every sample. ``need_path=False`` writes ``log_prob`` only.
+    ``out`` may pass preallocated tensors under the same keys."""
+    lib = load(require_gpu=True)
+    lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit)
+    dev = lt.device
+    B, T, U, _ = lt.shape
+    K = int(num_samples)
+    if uniform is None:
+        un = torch.rand((B, K, T), device=dev, dtype=torch.float32, generator=generator)
+    else:
+        un = _dev(uniform, torch.float32, "uniform")
+        if tuple(un.shape) != (B, K, T):
+            raise ValueError(f"uniform must be (B,K,T) = {(B, K, T)}")
+    out = dict(out or {})
+    lp = _buf(out, dev, "log_prob", (B, K), torch.float32)
+    pos = _buf(out, dev, "position", (B, K, T), torch.int32, want=need_path)
+    dur = _buf(out, dev, "duration", (B, K, U), torch.int32, want=need_path)
+    wsb = int(lib.ssnt_sample_align_workspace_size(B, T, U, K))
+    ws = _workspace(dev, wsb)
+    st = out.get("status")
+    if st is None:
+        st = _status(dev)
+    else:
+        st.zero_()
+    rc = lib.ssnt_sample_align_device(_p(lt), _p(lo), _p(sl), _p(pl), _p(un), B, T, U, K, flags,
+                                      _p(lp), _p(pos), _p(dur), _p(ws), wsb, _p(st), _stream(dev))
+    _finish("ssnt_sample_align", rc, st, check)
+    res = {"log_prob": lp, "uniform": un, "status": st}
     if need_path:
         res["position"] = pos
         res["duration"] = dur
