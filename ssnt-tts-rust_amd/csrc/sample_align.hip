@@ -3,74 +3,45 @@
 // Semantics: DESIGN.md 2.4. Forward filter, backward sample: the forward sweep is the alpha
 // recurrence of the forward-backward in split-exponent ("xf") f32; for every cell it leaves, per
 // sample k, the bit "uniform[k][s] * t < m'" (m' = the move term entering the cell, t = stay +
-// move, both at their common exponent). The backward walk is the best-path kernel's backtrace
-// (viterbi.hip) over those bits, one walk per sample. One workgroup = one utterance, 5 waves:
+// move, both at their common exponent). The structure (one chain wave, four loader waves, chunks,
+// decision words, the walk by runs) is align_dev.h's. What is this kernel's own:
 //
-//   wave 0      the chain: alpha[s][p] for s = 1..S-1. A lane holds K consecutive positions (p =
-//               K*lane + j, K = 1..16: one wave spans U <= 1024); the left neighbour of j = 0 is one
-//               DPP wave shift. Per sample and j one multiply and one compare; the compare's SGPR
-//               pair is the 64-bit decision word (bit `lane` of word j <-> position K*lane + j).
-//   waves 1..4  loaders: the rows of the next chunk (R rows) go global -> registers while the chain
-//               sweeps the current chunk, are converted there (exp() of the inputs as unnormalized
-//               xf, the clamp of the uniforms: nothing transcendental on the chain), then go to LDS
-//               transposed to [row][j][lane] as in viterbi.hip. Two LDS buffers, one workgroup
-//               barrier per chunk, range-checked buffer loads without predicates.
-//
-// Who takes the decisions (HELP, smp_help): as a rule the loader waves, a chunk behind the chain:
-// the chain leaves (t, m') of every cell in a third pair of LDS buffers, loader wave w decides the
-// rows w, w+4, ... of the previous chunk between issuing its loads and committing them (it alone
-// loads and reads those rows' uniforms, so the barrier per chunk is all the ordering needed). For
-// one sample on a long row (K >= 8) the chain wave decides itself (measured).
-//
-// Decision words: NS*T*K*8 bytes per utterance, laid out [sample][step][j], in LDS when they fit
-// beside the chunk buffers, else in the caller's workspace (ordinary vector stores by the deciding
-// wave; read back for the walks in blocks through the chunk buffers, which are free by then).
-//
-// Walks, same launch: sample k belongs to wave k mod 5. Each wave walks by runs (64 lanes test the
-// bit of the current position at 64 consecutive steps, one ballot finds the step that entered it),
-// fills its own start[] and writes duration / position from it, then sums the path's log-probability
-// sequentially in f32: 64 lanes gather 64 steps' terms, one lane order adds them.
+//   the chain   alpha[s][p] in xf form. Per sample and j one multiply and one compare; the compare
+//               is the decision word j of that sample and step.
+//   the loaders one position per load unit. The rows are converted in registers (exp() of the
+//               inputs as unnormalized xf, the clamp of the uniforms: nothing transcendental on the
+//               chain) on their way to LDS. The chunk's uniforms travel the same way.
+//   who decides (HELP, smp_help) in the helper form the chain leaves (t, m') of every cell in a
+//               third pair of LDS buffers, and loader wave w decides the rows w, w+4, ... of the
+//               previous chunk between issuing its loads and committing them (it alone loads and
+//               reads those rows' uniforms, so the barrier per chunk is all the ordering needed).
+//   the words   NS*T*K*8 bytes per utterance, [sample][step][j]; stored by the deciding wave.
+//   the walks   sample k belongs to wave k mod 5. Each wave reads back into its own share of the
+//               chunk buffers, walks, fills its own start[], writes duration / position from it and
+//               sums the path's log-probability in f32, 64 gathered terms at a time in step order.
 #include <hip/hip_runtime.h>
 
-#include <utility>
-
-#include "lattice_dev.h"
-#include "launch_util.h"
+#include "align_dev.h"
 
 namespace ssnt {
 namespace {
 
-constexpr int kSmpLoaders = 4;                        // loader waves
-constexpr int kSmpWaves = 1 + kSmpLoaders;
-constexpr int kSmpThreads = 64 * kSmpWaves;
-constexpr int kSmpUnits = 16;                         // positions per loader lane and chunk
-constexpr int kSmpMaxRpw = 8;                         // rows per loader wave and chunk, at most
-constexpr int kSmpMaxR = kSmpLoaders * kSmpMaxRpw;    // rows per chunk, at most
+constexpr int kSmpMaxR = kAlnLoaders * kAlnMaxRpw;    // rows per chunk, at most
 constexpr int kSmpMaxSamples = 64;
-constexpr int kSmpUUnits = kSmpMaxR * kSmpMaxSamples / (64 * kSmpLoaders);  // uniforms per loader lane and chunk
+constexpr int kSmpUUnits = kSmpMaxR * kSmpMaxSamples / (64 * kAlnLoaders);  // uniforms per loader lane and chunk
 constexpr int kSmpUStride = kSmpMaxSamples + 1;       // floats per row of the uniform buffer (padded)
-constexpr int kSmpJunk = 64;                          // elements behind each buffer: unused units' writes
-constexpr size_t kSmpHeadBytes = 64;
-constexpr int kSmpNoUnit = 0x7fffffff;                // byte offset no buffer range contains
+// elements behind each buffer, for unused units' writes: lane (< 64); no unit has a second half
+constexpr int kSmpJunk = 64;
 constexpr float kSmpUMax = 0x1.fffffep-1f;            // 1 - 2^-24
-
-extern "C" __device__ int smp_writelane(int v, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
 
 struct SmpShared {
   int feasible;
 };
 
-constexpr int smp_k(int U) { return U <= 64 ? 1 : U <= 128 ? 2 : U <= 256 ? 4 : U <= 512 ? 8 : 16; }
-constexpr int smp_kstride(int K) { return 64 + (K > 1 ? 32 / K : 0); }
 // Who takes the decisions (measured): the loader waves, a chunk behind the chain,
 // from (t, m') rows the chain leaves in LDS -- except one sample on a long row (K >= 8), where the
 // chain wave takes them itself.
-inline bool smp_help(int U, int NS) { return !(NS == 1 && smp_k(U) >= 8); }
-inline int smp_chunk_rows(int U) {
-  int r = kSmpUnits / ((U + 63) / 64);
-  r = r < 1 ? 1 : r > kSmpMaxRpw ? kSmpMaxRpw : r;
-  return kSmpLoaders * r;
-}
+inline bool smp_help(int U, int NS) { return !(NS == 1 && aln_k(U) >= 8); }
 struct SmpLayout {
   int K, R;
   bool help;
@@ -79,13 +50,13 @@ struct SmpLayout {
 // lds_bits: the decision words of the utterance in LDS (else: the workspace, no LDS of their own)
 inline SmpLayout smp_layout(int T, int U, int R, int NS, bool obs, bool lds_bits) {
   SmpLayout L{};
-  L.K = smp_k(U);
+  L.K = aln_k(U);
   L.R = R;
   L.help = smp_help(U, NS);
-  const size_t buf = (size_t)R * L.K * smp_kstride(L.K) + kSmpJunk;  // elements of one buffer
+  const size_t buf = (size_t)R * L.K * aln_kstride(L.K) + kSmpJunk;  // elements of one buffer
   const size_t ubuf = (size_t)R * kSmpUStride + kSmpJunk;
-  L.start_off = kSmpHeadBytes;
-  L.lt_off = (L.start_off + (size_t)kSmpWaves * (U + 2) * 4 + 15) & ~(size_t)15;
+  L.start_off = kAlnHeadBytes;
+  L.lt_off = (L.start_off + (size_t)kAlnWaves * (U + 2) * 4 + 15) & ~(size_t)15;
   L.ob_off = L.lt_off + 2 * buf * 16;
   L.u_off = L.ob_off + (obs ? 2 * buf * 8 : 0);
   L.tm_off = L.u_off + 2 * ubuf * 4;
@@ -93,15 +64,10 @@ inline SmpLayout smp_layout(int T, int U, int R, int NS, bool obs, bool lds_bits
   L.total = L.bits_off + (lds_bits ? (size_t)NS * T * L.K * 8 : 0);
   return L;
 }
-// the deepest chunk the unit count gives, shortened until everything fits LDS
+// one position per load unit; where LDS is short a chunk goes down to a single row
 inline SmpLayout smp_pick(int T, int U, int NS, bool obs, bool lds_bits) {
-  int R = smp_chunk_rows(U);
-  SmpLayout L = smp_layout(T, U, R, NS, obs, lds_bits);
-  while (L.total > kLdsBudget && R > 1) {
-    R = R > kSmpLoaders ? R - kSmpLoaders : R / 2;
-    L = smp_layout(T, U, R, NS, obs, lds_bits);
-  }
-  return L;
+  return aln_pick(aln_chunk_rows((U + 63) / 64), 1,
+                  [&](int r) { return smp_layout(T, U, r, NS, obs, lds_bits); });
 }
 // The decision words stay in LDS when they fit beside the chunk buffers the log_obs form has in
 // workspace mode (from the shape alone: the query does not know whether log_obs is given).
@@ -117,8 +83,8 @@ struct SmpParams {
 
 // WS: the decision words live in the workspace (else in LDS); HELP: the loader waves decide
 template <int K, bool OBS, bool WS, bool HELP>
-__global__ __launch_bounds__(kSmpThreads) void k_sample_align(SampleAlignArgs a, SmpParams q) {
-  constexpr int kKs = smp_kstride(K);
+__global__ __launch_bounds__(kAlnThreads) void k_sample_align(SampleAlignArgs a, SmpParams q) {
+  constexpr int kKs = aln_kstride(K);
   constexpr int kRow = K * kKs;  // LDS row stride in cells
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int b = blockIdx.x;
@@ -149,45 +115,37 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_align(SampleAlignArgs a,
                                 : reinterpret_cast<unsigned long long*>(smem + q.bits_off);
 
   auto fill_empty = [&]() {  // the infeasible rule, every sample
-    for (int k = tid; k < NS; k += kSmpThreads) lp_out[k] = ninf;
+    for (int k = tid; k < NS; k += kAlnThreads) lp_out[k] = ninf;
     if (pos_out)
-      for (int s = tid; s < NS * T; s += kSmpThreads) pos_out[s] = -1;
+      for (int s = tid; s < NS * T; s += kAlnThreads) pos_out[s] = -1;
     if (dur_out)
-      for (int p = tid; p < NS * U; p += kSmpThreads) dur_out[p] = 0;
+      for (int p = tid; p < NS * U; p += kAlnThreads) dur_out[p] = 0;
   };
-  if (!(S >= 1 && P >= 1 && S <= T && P <= U && S >= P)) {
-    if ((S > T || P > U || S < 0 || P < 0) && a.status && tid == 0) atomicOr(a.status, kStatusBadLength);
+  if (!aln_lengths_ok(S, P, T, U, a.status, tid)) {
     fill_empty();
     return;
   }
 
-  // ------------------------------------------------------------------ loaders: chunk geometry
-  // Loader wave w takes rows w, w+4, ... of a chunk; its lanes stride across a row, one position
-  // per unit. goff = byte offset from the chunk's first row (kSmpNoUnit for a unit outside the
-  // geometry: its load is out of every range), loff = LDS cell in the buffer (the junk behind it
-  // for such a unit). The uniforms of a chunk: row i of sample k at ugoff, to uloff = [i][k].
+  // ------------------------------------------------------------------ loaders
+  // The uniforms of a chunk: row i of sample k at ugoff, to uloff = [i][k].
   const int NC = (S - 1 + R - 1) / R;  // chunks of transition rows 0..S-2
-  int goff[kSmpUnits], loff[kSmpUnits], ugoff[kSmpUUnits], uloff[kSmpUUnits];
-  f32x2 lreg[kSmpUnits];
-  float oreg[OBS ? kSmpUnits : 1], ureg[kSmpUUnits];
+  int goff[kAlnUnits], loff[kAlnUnits], ugoff[kSmpUUnits], uloff[kSmpUUnits];
+  f32x2 lreg[kAlnUnits];
+  float oreg[OBS ? kAlnUnits : 1], ureg[kSmpUUnits];
   const bool loader = wave >= 1;
   if (loader) {
     const int w = wave - 1;
     const int upr = (U + 63) / 64;  // units per row and lane
-    static_for<kSmpUnits>([&](auto Ic) __attribute__((always_inline)) {
+    static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
       constexpr int u = decltype(Ic)::value;
-      const int row = w + kSmpLoaders * (u / upr);
-      const int p = lane + 64 * (u % upr);
-      const bool ok = row < R && p < U;
-      goff[u] = ok ? (row * U + p) * 8 : kSmpNoUnit;
-      loff[u] = ok ? row * kRow + (p % K) * kKs + p / K : R * kRow + lane;
+      aln_unit<K>(w, lane, u, upr, 1, 8, R, U, goff[u], loff[u]);
     });
     static_for<kSmpUUnits>([&](auto Ic) __attribute__((always_inline)) {
       constexpr int u = decltype(Ic)::value;
       const int f = u * 64 + lane;  // this wave's rows w, w+4, ... only: it alone reads them back
-      const int i = w + kSmpLoaders * (f % kSmpMaxRpw), k = f / kSmpMaxRpw;
+      const int i = w + kAlnLoaders * (f % kAlnMaxRpw), k = f / kAlnMaxRpw;
       const bool ok = i < R && k < NS;
-      ugoff[u] = ok ? (k * T + i) * 4 : kSmpNoUnit;
+      ugoff[u] = ok ? (k * T + i) * 4 : kAlnNoUnit;
       uloff[u] = ok ? i * kSmpUStride + k : R * kSmpUStride + lane;
     });
   }
@@ -197,15 +155,15 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_align(SampleAlignArgs a,
     const int r0 = c * R;
     const int n = min(R, S - 1 - r0);
     const __amdgpu_buffer_rsrc_t rs = brsrc(lt + (size_t)r0 * U * 2, (unsigned)(n * U) * 8u);
-    static_for<kSmpUnits>([&](auto Ic) __attribute__((always_inline)) {
+    static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
       constexpr int u = decltype(Ic)::value;
       lreg[u] = rbuf_ld2(rs, goff[u], 0, 0);
     });
     if constexpr (OBS) {
       const __amdgpu_buffer_rsrc_t ro = brsrc(lo + (size_t)(r0 + 1) * U, (unsigned)(n * U) * 4u);
-      static_for<kSmpUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
-        oreg[u] = rbuf_ld1(ro, goff[u] == kSmpNoUnit ? kSmpNoUnit : goff[u] >> 1, 0, 0);
+        oreg[u] = rbuf_ld1(ro, goff[u] == kAlnNoUnit ? kAlnNoUnit : goff[u] >> 1, 0, 0);
       });
     }
     // the range ends with row r0 + n of the last sample (r0 + n <= S - 1 < T: inside the tensor)
@@ -219,7 +177,7 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_align(SampleAlignArgs a,
   // clamped uniforms (NaN -> 0)
   auto commit = [&](int c) __attribute__((always_inline)) {
     float4* dst = ltb + (size_t)(c & 1) * bufsz;
-    static_for<kSmpUnits>([&](auto Ic) __attribute__((always_inline)) {
+    static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
       constexpr int u = decltype(Ic)::value;
       float me, ms;
       int ee, es;
@@ -228,7 +186,7 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_align(SampleAlignArgs a,
     });
     if constexpr (OBS) {
       float2* dsto = obb + (size_t)(c & 1) * bufsz;
-      static_for<kSmpUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
         const xf o = xf_exp(oreg[u], true);
         dsto[loff[u]] = make_float2(o.m, __builtin_bit_cast(float, o.e));
@@ -266,12 +224,9 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_align(SampleAlignArgs a,
 #pragma unroll
       for (int j = 0; j < K; ++j) {
         const bool mv = uk * tt[j] < mp[j];
-        const unsigned long long w = __ballot(mv);
-        mlo = smp_writelane((int)(unsigned)w, j, mlo);
-        mhi = smp_writelane((int)(unsigned)(w >> 32), j, mhi);
+        aln_put_word(__ballot(mv), j, mlo, mhi);
       }
-      const unsigned long long myw = ((unsigned long long)(unsigned)mhi << 32) | (unsigned)mlo;
-      if (lane < K) dst[(size_t)k * T * K + lane] = myw;
+      if (lane < K) dst[(size_t)k * T * K + lane] = aln_my_word(mlo, mhi);
     }
   };
   // helper form: loader wave w decides rows w, w+4, ... of chunk c from the chain's (t, m') rows
@@ -280,7 +235,7 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_align(SampleAlignArgs a,
     const int n = min(R, S - 1 - r0);
     const float2* TM = tmb + (size_t)(c & 1) * R * K * 64 + lane;
     const float* UB = ubb + (size_t)(c & 1) * ubufsz + lane;
-    for (int i = wave - 1; i < n; i += kSmpLoaders) {
+    for (int i = wave - 1; i < n; i += kAlnLoaders) {
       float tt[K], mp[K];
 #pragma unroll
       for (int j = 0; j < K; ++j) {
@@ -301,7 +256,6 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_align(SampleAlignArgs a,
     if (HELP && loader && c > 0) help(c - 1);
     if (wave == 0) {
       const int r0 = c * R;
-      const int n = min(R, S - 1 - r0);
       const float4* Bf = ltb + (size_t)(c & 1) * bufsz + lane;
       const float2* OB = obb + (size_t)(c & 1) * bufsz + lane;
       const float* UB = ubb + (size_t)(c & 1) * ubufsz + lane;
@@ -357,6 +311,8 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_align(SampleAlignArgs a,
           decide(tt, mp, r.u, s);
         }
       };
+      // two rows in registers: the next row's LDS reads go out before this row's arithmetic
+      const int n = min(R, S - 1 - r0);
       Row ra, rb;
       ld(ra, 0);
       int i = 0;
@@ -392,64 +348,31 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_align(SampleAlignArgs a,
   // ------------------------------------------------------------------ one walk per sample
   int* start = startb + wave * (U + 2);
   // workspace mode: this wave's share of the chunk buffers holds walk_rows rows of one sample
-  const int region = (4 * bufsz / kSmpWaves) / K * K;  // 8-byte words (a cell of the buffer is two)
+  const int region = (4 * bufsz / kAlnWaves) / K * K;  // 8-byte words (a cell of the buffer is two)
   unsigned long long* wbuf = reinterpret_cast<unsigned long long*>(ltb) + (size_t)wave * region;
   const int walk_rows = region / K;
-  auto pos_of = [&](int s) {  // the last p with start[p] <= s (start[0] = 0, increasing)
-    int lo_p = 0, hi_p = P - 1;
-    while (lo_p < hi_p) {
-      const int mid = (lo_p + hi_p + 1) >> 1;
-      if (start[mid] <= s) lo_p = mid; else hi_p = mid - 1;
-    }
-    return lo_p;
-  };
-  for (int k = wave; k < NS; k += kSmpWaves) {
+  auto pos_of = [&](int s) { return aln_pos_of(start, P, s); };
+  for (int k = wave; k < NS; k += kAlnWaves) {
     cbar();
     for (int p = lane; p < P; p += 64) start[p] = 0;
     if (lane == 0) start[P] = S;
     const unsigned long long* kb = bits + (size_t)k * T * K;
-    int s = S - 1, p = P - 1;
-    while (p > 0 && s >= 1) {
+    AlnAt at{S - 1, P - 1};
+    while (at.p > 0 && at.s >= 1) {
       int lo_row = 0;
       const unsigned long long* wb = kb;
       if constexpr (WS) {  // rows [lo_row, s] of the sample -> this wave's LDS
-        lo_row = max(1, s - walk_rows + 1);
-        const unsigned long long* src = kb + (size_t)lo_row * K;
-        const int nw = (s - lo_row + 1) * K;
+        lo_row = max(1, at.s - walk_rows + 1);
         cbar();
-        for (int j0 = lane; j0 < nw; j0 += 8 * 64) {  // 8 loads in flight per lane
-          unsigned long long t[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i)
-            t[i] = __hip_atomic_load(src + min(j0 + i * 64, nw - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-          for (int i = 0; i < 8; ++i)
-            if (j0 + i * 64 < nw) wbuf[j0 + i * 64] = t[i];
-        }
+        aln_read_back<64>(kb + (size_t)lo_row * K, wbuf, (at.s - lo_row + 1) * K, lane);
         cbar();
         wb = wbuf;
       }
-      const int first = max(lo_row, 1);
-      while (p > 0 && s >= first) {
-        const int ss = s - lane;
-        int bit = 0;
-        if (ss >= first) bit = (int)((wb[(size_t)(ss - lo_row) * K + (p & (K - 1))] >> (p / K)) & 1ull);
-        const unsigned long long m = __ballot(bit != 0);
-        if (m == 0) {
-          s = max(s - 64, first - 1);
-        } else {  // the nearest step below s that entered p
-          const int st = s - (__ffsll((long long)m) - 1);
-          if (lane == 0) start[p] = st;
-          s = st - 1;
-          p = p - 1;
-        }
-      }
+      at = aln_walk<K>(wb, lo_row, max(lo_row, 1), lane, start, at.s, at.p);
     }
     cbar();
-    if (dur_out)
-      for (int pp = lane; pp < U; pp += 64) dur_out[(size_t)k * U + pp] = pp < P ? start[pp + 1] - start[pp] : 0;
-    if (pos_out)
-      for (int ss = lane; ss < T; ss += 64) pos_out[(size_t)k * T + ss] = ss < S ? pos_of(ss) : -1;
+    aln_write_path<64>(start, S, P, T, U, dur_out ? dur_out + (size_t)k * U : nullptr,
+                       pos_out ? pos_out + (size_t)k * T : nullptr, lane);
     // log_prob: the sequential f32 sum of DESIGN.md 2.4, 64 steps' terms gathered at a time
     float v = OBS ? lo[0] : 0.0f;
     for (int s0 = 0; s0 < S - 1; s0 += 64) {
@@ -474,54 +397,42 @@ __global__ __launch_bounds__(kSmpThreads) void k_sample_align(SampleAlignArgs a,
 
 template <int K, bool OBS, bool WS>
 int launch_sample_k(const SampleAlignArgs& a, const SmpLayout& L, hipStream_t st) {
-  SmpParams q{};
-  q.R = L.R;
-  q.start_off = (unsigned)L.start_off; q.lt_off = (unsigned)L.lt_off; q.ob_off = (unsigned)L.ob_off;
-  q.u_off = (unsigned)L.u_off; q.tm_off = (unsigned)L.tm_off; q.bits_off = (unsigned)L.bits_off;
+  const SmpParams q{L.R, (unsigned)L.start_off, (unsigned)L.lt_off, (unsigned)L.ob_off,
+                    (unsigned)L.u_off, (unsigned)L.tm_off, (unsigned)L.bits_off};
   if (L.help)
-    return launch_lds(k_sample_align<K, OBS, WS, true>, dim3(a.B), dim3(kSmpThreads), L.total, kLdsBudget, st, a, q);
-  return launch_lds(k_sample_align<K, OBS, WS, false>, dim3(a.B), dim3(kSmpThreads), L.total, kLdsBudget, st, a, q);
-}
-
-template <bool OBS, bool WS>
-int launch_sample_obs(const SampleAlignArgs& a, const SmpLayout& L, hipStream_t st) {
-  switch (L.K) {
-    case 1: return launch_sample_k<1, OBS, WS>(a, L, st);
-    case 2: return launch_sample_k<2, OBS, WS>(a, L, st);
-    case 4: return launch_sample_k<4, OBS, WS>(a, L, st);
-    case 8: return launch_sample_k<8, OBS, WS>(a, L, st);
-    default: return launch_sample_k<16, OBS, WS>(a, L, st);
-  }
+    return launch_lds(k_sample_align<K, OBS, WS, true>, dim3(a.B), dim3(kAlnThreads), L.total, kLdsBudget, st, a, q);
+  return launch_lds(k_sample_align<K, OBS, WS, false>, dim3(a.B), dim3(kAlnThreads), L.total, kLdsBudget, st, a, q);
 }
 
 }  // namespace
 
 size_t sample_align_workspace_bytes(int B, int T, int U, int NS) {
   if (smp_bits_fit(T, U, NS)) return 0;
-  return (size_t)B * NS * T * smp_k(U) * 8;
+  return (size_t)B * NS * T * aln_k(U) * 8;
 }
 
 int launch_sample_align(const SampleAlignArgs& a, hipStream_t st) {
-  if (a.B < 0 || a.T < 0 || a.U < 0 || (a.flags & ~SSNT_FLAG_TERMINAL_EMIT)) return SSNT_ERR_INVALID_ARG;
+  // (NS and uniform: each beside the shared checks that return the same code, so no precedence moves)
   if (a.NS < 1 || a.NS > kSmpMaxSamples) return SSNT_ERR_INVALID_ARG;
-  if (a.B == 0) return SSNT_OK;
-  if (!a.log_trans || !a.step_len || !a.pos_len || !a.uniform || !a.log_prob) return SSNT_ERR_INVALID_ARG;
-  if (a.U > 1024) return SSNT_ERR_UNSUPPORTED;
-  if (!aligned_to(a.log_trans, 8) || !aligned_to(a.log_obs, 4) || !aligned_to(a.uniform, 4))
-    return SSNT_ERR_UNSUPPORTED;
+  const int rc = aln_check_args(a.B, a.T, a.U, a.flags,
+                                a.log_trans && a.step_len && a.pos_len && a.uniform && a.log_prob, a.log_trans,
+                                a.log_obs);
+  if (rc != SSNT_OK || a.B == 0) return rc;
+  if (!aligned_to(a.uniform, 4)) return SSNT_ERR_UNSUPPORTED;
   // the byte offsets of the range-checked loads are 32-bit
-  if ((size_t)a.NS * a.T * 4 >= (size_t)kSmpNoUnit) return SSNT_ERR_UNSUPPORTED;
+  if ((size_t)a.NS * a.T * 4 >= (size_t)kAlnNoUnit) return SSNT_ERR_UNSUPPORTED;
   const bool obs = a.log_obs != nullptr;
   const int U = a.U > 0 ? a.U : 1;  // (T == 0 or U == 0: every utterance is infeasible)
   const bool fit = a.T == 0 || a.U == 0 || smp_bits_fit(a.T, U, a.NS);
-  if (!fit) {
-    const size_t need = sample_align_workspace_bytes(a.B, a.T, a.U, a.NS);
-    if (!a.workspace || a.workspace_bytes < need || !aligned_to(a.workspace, 8)) return SSNT_ERR_WORKSPACE;
-  }
+  if (!fit && !aln_workspace_ok(a.workspace, a.workspace_bytes, sample_align_workspace_bytes(a.B, a.T, a.U, a.NS)))
+    return SSNT_ERR_WORKSPACE;
   const SmpLayout L = smp_pick(a.T, U, a.NS, obs, fit);
   if (L.total > kLdsBudget) return SSNT_ERR_UNSUPPORTED;
-  if (fit) return obs ? launch_sample_obs<true, false>(a, L, st) : launch_sample_obs<false, false>(a, L, st);
-  return obs ? launch_sample_obs<true, true>(a, L, st) : launch_sample_obs<false, true>(a, L, st);
+  return aln_with_k(L.K, [&](auto Kc) {
+    constexpr int K = decltype(Kc)::value;
+    if (fit) return obs ? launch_sample_k<K, true, false>(a, L, st) : launch_sample_k<K, false, false>(a, L, st);
+    return obs ? launch_sample_k<K, true, true>(a, L, st) : launch_sample_k<K, false, true>(a, L, st);
+  });
 }
 
 }  // namespace ssnt

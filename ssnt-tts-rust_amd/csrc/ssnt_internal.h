@@ -1,5 +1,5 @@
-// ssnt_internal.h -- launchers shared between the kernel files (fwd_bwd_*.hip, decode.hip) and the
-// C-ABI host layer (capi.hip). Not part of the public interface (that is include/ssnt_tts_c.h).
+// ssnt_internal.h -- launchers shared between the kernel files (fwd_bwd*.hip, v2_*.hip, viterbi.hip,
+// sample_align.hip, decode.hip, fused_decode.hip) and the C-ABI host layer (capi.hip). Not part of the public interface (that is include/ssnt_tts_c.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

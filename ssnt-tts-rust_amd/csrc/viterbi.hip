@@ -2,48 +2,27 @@
 //
 // Semantics: DESIGN.md 2.2. A max-plus sweep over the (B,T,U,2) tensor of the forward-backward:
 // f32 adds and one strict compare per cell, no reassociation, so every form is bit-identical to
-// the plain f32 restatement (tests/viterbi_ref.py). One workgroup = one utterance, 5 waves:
+// the plain f32 restatement (tests/viterbi_ref.py). The structure (one chain wave, four loader
+// waves, chunks, decision words, the walk by runs) is align_dev.h's. What is this kernel's own:
 //
-//   wave 0      the chain: V[s][p] for s = 1..S-1. A lane holds K consecutive positions
-//               (p = K*lane + k, K = 1..16, so one wave spans U <= 1024 and no row needs a
-//               cross-wave neighbour); the left neighbour of k = 0 is one DPP wave shift. The
-//               compare of each k lands in an SGPR pair, which is that step's 64-bit backpointer
-//               word (bit `lane` of word k <-> position K*lane + k).
-//   waves 1..4  loaders: the rows of the next chunk (R rows) go global -> registers while the
-//               chain sweeps the current chunk, then registers -> LDS, transposed to [row][k][lane]
-//               (k-planes padded by 32/K so both the loaders' writes and the chain's reads are
-//               bank-conflict free). Two LDS buffers, one workgroup barrier per chunk: the load
-//               latency of a chunk hides behind R chain steps. The loads are range-checked
-//               buffer loads, all issued back to back (no predicate, so no wait between them).
-//
-// Backpointer words: T*K*8 bytes per utterance, in LDS when they fit beside the buffers, else in
-// the caller's workspace (staged through LDS, flushed 64 rows at a time with vector stores, and
-// read back for the backtrace in blocks as large as the two chunk buffers, which are free by
-// then). With no path output nothing is kept.
-//
-// Backtrace, same launch: the path is monotone, so wave 0 walks it by runs: 64 lanes test the
-// bit of the current position at 64 consecutive steps, one ballot finds the step that entered
-// the position. At most (P-1) + S/64 LDS round trips instead of S. start[p] (the first step at
-// p) then gives duration[p] = start[p+1] - start[p] and position[s] by a binary search, both
-// written by all waves.
+//   the chain   V[s][p] in f32; the compare of each k is that step's backpointer word k.
+//   the loaders log_trans moves in 16-byte units (two positions) when it is 16-byte aligned with
+//               even U, else in 8-byte units; log_obs as single floats. Nothing is converted.
+//   the words   T*K*8 bytes per utterance. In workspace mode they are staged through LDS and
+//               flushed 64 rows at a time with vector stores, and read back for the backtrace in
+//               blocks as large as the two chunk buffers. With no path output nothing is kept.
+//   the walk    wave 0 walks; all waves read a block back and write duration and position.
 #include <hip/hip_runtime.h>
 
-#include <utility>
-
-#include "lattice_dev.h"
-#include "launch_util.h"
+#include "align_dev.h"
 
 namespace ssnt {
 namespace {
 
-constexpr int kVitLoaders = 4;                        // loader waves
-constexpr int kVitThreads = 64 * (1 + kVitLoaders);
-constexpr int kVitUnits = 16;                         // load units per loader lane and chunk
-constexpr int kVitMaxRpw = 8;                         // rows per loader wave and chunk, at most
 constexpr int kVitStageRows = 64;                     // workspace mode: rows staged per flush
-constexpr int kVitJunk = 160;                         // elements behind each buffer: unused units' writes
-constexpr size_t kVitHeadBytes = 64;
-constexpr int kVitNoUnit = 0x7fffffff;                // byte offset no buffer range contains
+// elements behind each buffer, for unused units' writes: lane (< 64) and, for the second half of
+// a 16-byte unit, kKs (<= 80) further
+constexpr int kVitJunk = 160;
 
 // shr1 (lattice_dev.h) with -inf for lane 0: the lane without a source keeps `old`. No select on
 // the lane index around it -- a DPP read of a lane that EXEC masks off counts as "no source", and
@@ -53,25 +32,10 @@ __device__ __forceinline__ float shr1_ninf(float x) {
                                                                0x138, 0xf, 0xf, false));
 }
 
-// v_writelane_b32: lane `lane` of the result holds the wave-uniform `v`, the other lanes keep `old`
-// (bound to the LLVM intrinsic by name, as buffer_ops.h does: this toolchain has no clang builtin)
-extern "C" __device__ int vit_writelane(int v, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
-
 struct VitShared {
   int feasible, s, p;
 };
 
-constexpr int vit_k(int U) { return U <= 64 ? 1 : U <= 128 ? 2 : U <= 256 ? 4 : U <= 512 ? 8 : 16; }
-constexpr int vit_kstride(int K) { return 64 + (K > 1 ? 32 / K : 0); }  // float2 / float units
-// Rows per chunk. A loader lane moves kVitUnits units per chunk: 16-byte units (two positions)
-// when log_trans is 16-byte aligned with even U and there is no log_obs, else one position per
-// unit (log_obs moves as single floats, so it sets the unit count whenever it is there).
-inline int vit_chunk_rows(int U, bool wide_units) {
-  const int per_row = wide_units ? (U + 127) / 128 : (U + 63) / 64;
-  int r = kVitUnits / per_row;
-  r = r < 1 ? 1 : r > kVitMaxRpw ? kVitMaxRpw : r;
-  return kVitLoaders * r;
-}
 struct VitLayout {
   int K, R;
   size_t start_off, lt_off, ob_off, bits_off, total;  // bytes
@@ -79,10 +43,10 @@ struct VitLayout {
 // mode: 0 no backpointers, 1 backpointer words in LDS, 2 in the workspace (stage rows)
 inline VitLayout vit_layout(int T, int U, int R, bool obs, int mode) {
   VitLayout L{};
-  L.K = vit_k(U);
+  L.K = aln_k(U);
   L.R = R;
-  const size_t buf = (size_t)R * L.K * vit_kstride(L.K) + kVitJunk;  // elements of one buffer
-  L.start_off = kVitHeadBytes;
+  const size_t buf = (size_t)R * L.K * aln_kstride(L.K) + kVitJunk;  // elements of one buffer
+  L.start_off = kAlnHeadBytes;
   L.lt_off = (L.start_off + (size_t)(U + 2) * 4 + 15) & ~(size_t)15;
   L.ob_off = L.lt_off + 2 * buf * 8;
   L.bits_off = L.ob_off + (obs ? 2 * buf * 4 : 0);
@@ -90,15 +54,12 @@ inline VitLayout vit_layout(int T, int U, int R, bool obs, int mode) {
                           : mode == 2 ? (size_t)kVitStageRows * L.K * 8 : 0);
   return L;
 }
-// the deepest chunk the unit count gives, shortened until everything fits LDS
+// A loader lane moves 16-byte units (two positions) when log_trans is 16-byte aligned with even U
+// and there is no log_obs, else one position per unit (log_obs moves as single floats, so it sets
+// the unit count whenever it is there). A chunk keeps at least one row per loader wave.
 inline VitLayout vit_pick(int T, int U, bool wide_units, bool obs, int mode) {
-  int R = vit_chunk_rows(U, wide_units);
-  VitLayout L = vit_layout(T, U, R, obs, mode);
-  while (L.total > kLdsBudget && R > kVitLoaders) {
-    R -= kVitLoaders;
-    L = vit_layout(T, U, R, obs, mode);
-  }
-  return L;
+  const int R = aln_chunk_rows(wide_units ? (U + 127) / 128 : (U + 63) / 64);
+  return aln_pick(R, kAlnLoaders, [&](int r) { return vit_layout(T, U, r, obs, mode); });
 }
 // The backpointer words stay in LDS when they fit beside the chunk buffers the log_obs form has
 // in workspace mode (from the shape alone: the query knows neither log_obs nor the alignment).
@@ -115,8 +76,8 @@ struct VitParams {
 
 // MODE: 0 no path output (no backpointers), 1 backpointer words in LDS, 2 in the workspace
 template <int K, bool OBS, int MODE>
-__global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParams q) {
-  constexpr int kKs = vit_kstride(K);
+__global__ __launch_bounds__(kAlnThreads) void k_viterbi(ViterbiArgs a, VitParams q) {
+  constexpr int kKs = aln_kstride(K);
   constexpr int kRow = K * kKs;  // LDS row stride (float2 units for log_trans, floats for log_obs)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int b = blockIdx.x;
@@ -148,46 +109,31 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
 
   auto fill_empty = [&]() {  // the infeasible rule: every position -1, every duration 0
     if (pos_out)
-      for (int s = tid; s < T; s += kVitThreads) pos_out[s] = -1;
+      for (int s = tid; s < T; s += kAlnThreads) pos_out[s] = -1;
     if (dur_out)
-      for (int p = tid; p < U; p += kVitThreads) dur_out[p] = 0;
+      for (int p = tid; p < U; p += kAlnThreads) dur_out[p] = 0;
   };
-  if (!(S >= 1 && P >= 1 && S <= T && P <= U && S >= P)) {
-    if ((S > T || P > U || S < 0 || P < 0) && a.status && tid == 0) atomicOr(a.status, kStatusBadLength);
+  if (!aln_lengths_ok(S, P, T, U, a.status, tid)) {
     if (tid == 0) a.log_prob[b] = ninf;
     fill_empty();
     return;
   }
 
-  // ------------------------------------------------------------------ loaders: chunk geometry
-  // Loader wave w takes rows w, w+4, ... of a chunk; its lanes stride across a row. Everything
-  // but the chunk's base is chunk-invariant, so the offsets are formed once: goff = byte offset
-  // from the chunk's first row (kVitNoUnit for a unit outside the geometry: its load is out of
-  // every range), loff = LDS element in the buffer (the junk behind it for such a unit).
+  // ------------------------------------------------------------------ loaders
   const int NC = (S - 1 + R - 1) / R;  // chunks of transition rows 0..S-2
-  int goff[kVitUnits], loff[kVitUnits], goffo[OBS ? kVitUnits : 1], loffo[OBS ? kVitUnits : 1];
-  f32x4 lreg[kVitUnits];
-  float oreg[OBS ? kVitUnits : 1];
+  int goff[kAlnUnits], loff[kAlnUnits], goffo[OBS ? kAlnUnits : 1], loffo[OBS ? kAlnUnits : 1];
+  f32x4 lreg[kAlnUnits];
+  float oreg[OBS ? kAlnUnits : 1];
   const bool loader = wave >= 1;
   if (loader) {
-    const int w = wave - 1;
     const int ppu = q.vec ? 2 : 1;                       // positions per log_trans unit
     const int upr = (U + 64 * ppu - 1) / (64 * ppu);     // units per row and lane
     const int upro = (U + 63) / 64;
-    static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+    const int w = wave - 1;
+    static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
       constexpr int u = decltype(Ic)::value;
-      const int row = w + kVitLoaders * (u / upr);
-      const int p = (lane + 64 * (u % upr)) * ppu;
-      const bool ok = row < R && p < U;
-      goff[u] = ok ? (row * U + p) * 8 : kVitNoUnit;
-      loff[u] = ok ? row * kRow + (p % K) * kKs + p / K : R * kRow + lane;
-      if constexpr (OBS) {
-        const int rowo = w + kVitLoaders * (u / upro);
-        const int po = lane + 64 * (u % upro);
-        const bool oko = rowo < R && po < U;
-        goffo[u] = oko ? (rowo * U + po) * 4 : kVitNoUnit;
-        loffo[u] = oko ? rowo * kRow + (po % K) * kKs + po / K : R * kRow + lane;
-      }
+      aln_unit<K>(w, lane, u, upr, ppu, 8, R, U, goff[u], loff[u]);
+      if constexpr (OBS) aln_unit<K>(w, lane, u, upro, 1, 4, R, U, goffo[u], loffo[u]);
     });
   }
   // global -> registers: rows [c*R, min(c*R + R, S-1))
@@ -196,12 +142,12 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
     const int n = min(R, S - 1 - r0);
     const __amdgpu_buffer_rsrc_t rs = brsrc(lt + (size_t)r0 * U * 2, (unsigned)(n * U) * 8u);
     if (q.vec) {
-      static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
         lreg[u] = rbuf_ld4(rs, goff[u], 0, 0);
       });
     } else {
-      static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
         const f32x2 v = rbuf_ld2(rs, goff[u], 0, 0);
         lreg[u].x = v.x; lreg[u].y = v.y;
@@ -209,7 +155,7 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
     }
     if constexpr (OBS) {  // log_obs rows [c*R + 1, ...): the row a step adds is its own
       const __amdgpu_buffer_rsrc_t ro = brsrc(lo + (size_t)(r0 + 1) * U, (unsigned)(n * U) * 4u);
-      static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
         oreg[u] = rbuf_ld1(ro, goffo[u], 0, 0);
       });
@@ -219,20 +165,20 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
   auto commit = [&](int c) __attribute__((always_inline)) {
     float2* dst = ltb + (size_t)(c & 1) * bufsz;
     if (q.vec) {
-      static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
         dst[loff[u]] = make_float2(lreg[u].x, lreg[u].y);
         dst[loff[u] + (K == 1 ? 1 : kKs)] = make_float2(lreg[u].z, lreg[u].w);
       });
     } else {
-      static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
         dst[loff[u]] = make_float2(lreg[u].x, lreg[u].y);
       });
     }
     if constexpr (OBS) {
       float* dsto = obb + (size_t)(c & 1) * bufsz;
-      static_for<kVitUnits>([&](auto Ic) __attribute__((always_inline)) {
+      static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
         constexpr int u = decltype(Ic)::value;
         dsto[loffo[u]] = oreg[u];
       });
@@ -254,7 +200,6 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
     if (loader && c + 1 < NC) issue(c + 1);
     if (wave == 0) {
       const int r0 = c * R;
-      const int n = min(R, S - 1 - r0);
       const float2* B = ltb + (size_t)(c & 1) * bufsz + lane;
       const float* OB = obb + (size_t)(c & 1) * bufsz + lane;
       struct Row {
@@ -282,14 +227,9 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
           float v = bp ? move : stay;
           if constexpr (OBS) v = v + r.o[k];
           V[k] = v;
-          if constexpr (MODE != 0) {
-            // the compare's SGPR pair goes straight into lane k (v_writelane: no select, no copy)
-            const unsigned long long w = __ballot(bp);
-            mlo = vit_writelane((int)(unsigned)w, k, mlo);
-            mhi = vit_writelane((int)(unsigned)(w >> 32), k, mhi);
-          }
+          if constexpr (MODE != 0) aln_put_word(__ballot(bp), k, mlo, mhi);
         }
-        const unsigned long long myw = ((unsigned long long)(unsigned)mhi << 32) | (unsigned)mlo;
+        const unsigned long long myw = aln_my_word(mlo, mhi);
         if constexpr (MODE == 1) {
           if (lane < K) bits[(size_t)s * K + lane] = myw;
         } else if constexpr (MODE == 2) {
@@ -302,6 +242,7 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
         }
       };
       // two rows in registers: the next row's LDS reads go out before this row's arithmetic
+      const int n = min(R, S - 1 - r0);
       Row ra, rb;
       ld(ra, 0);
       int i = 0;
@@ -340,7 +281,7 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
   }
 
   // ------------------------------------------------------------------ backtrace by runs
-  for (int p = tid; p < P; p += kVitThreads) start[p] = 0;
+  for (int p = tid; p < P; p += kAlnThreads) start[p] = 0;
   if (tid == 0) start[P] = S;
   for (;;) {
     __syncthreads();
@@ -348,113 +289,58 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(ViterbiArgs a, VitParam
     if (p <= 0 || s < 1) break;
     int lo_row = 0;
     const unsigned long long* wb = bits;
-    if constexpr (MODE == 2) {  // rows [lo_row, s] of the workspace -> LDS
+    if constexpr (MODE == 2) {  // rows [lo_row, s] of the workspace -> LDS, by all waves
       lo_row = max(1, s - walk_rows + 1);
-      unsigned long long* src = ws + (size_t)lo_row * K;
-      const int nw = (s - lo_row + 1) * K;
-      for (int j0 = tid; j0 < nw; j0 += 8 * kVitThreads) {  // 8 loads in flight per lane
-        unsigned long long t[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          t[i] = __hip_atomic_load(src + min(j0 + i * kVitThreads, nw - 1), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          if (j0 + i * kVitThreads < nw) wbuf[j0 + i * kVitThreads] = t[i];
-      }
+      aln_read_back<kAlnThreads>(ws + (size_t)lo_row * K, wbuf, (s - lo_row + 1) * K, tid);
       wb = wbuf;
     }
-    const int first = max(lo_row, 1);
     __syncthreads();
     if (wave == 0) {
-      while (p > 0 && s >= first) {
-        const int ss = s - lane;
-        int bit = 0;
-        if (ss >= first) bit = (int)((wb[(size_t)(ss - lo_row) * K + (p & (K - 1))] >> (p / K)) & 1ull);
-        const unsigned long long m = __ballot(bit != 0);
-        if (m == 0) {
-          s = max(s - 64, first - 1);
-        } else {  // the nearest step below s that entered p
-          const int st = s - (__ffsll((long long)m) - 1);
-          if (lane == 0) start[p] = st;
-          s = st - 1;
-          p = p - 1;
-        }
-      }
+      const AlnAt at = aln_walk<K>(wb, lo_row, max(lo_row, 1), lane, start, s, p);
       if (lane == 0) {
-        sh->s = s;
-        sh->p = p;
+        sh->s = at.s;
+        sh->p = at.p;
       }
     }
   }
 
   // ------------------------------------------------------------------ outputs
-  if (dur_out)
-    for (int p = tid; p < U; p += kVitThreads) dur_out[p] = p < P ? start[p + 1] - start[p] : 0;
-  if (pos_out)
-    for (int s = tid; s < T; s += kVitThreads) {
-      int r = -1;
-      if (s < S) {  // the last p with start[p] <= s (start[0] = 0, increasing)
-        int lo_p = 0, hi_p = P - 1;
-        while (lo_p < hi_p) {
-          const int mid = (lo_p + hi_p + 1) >> 1;
-          if (start[mid] <= s) lo_p = mid; else hi_p = mid - 1;
-        }
-        r = lo_p;
-      }
-      pos_out[s] = r;
-    }
+  aln_write_path<kAlnThreads>(start, S, P, T, U, dur_out, pos_out, tid);
 }
 
 template <int K, bool OBS, int MODE>
 int launch_viterbi_k(const ViterbiArgs& a, const VitLayout& L, bool vec, hipStream_t st) {
-  VitParams q{};
-  q.R = L.R;
-  q.vec = vec;
-  q.start_off = (unsigned)L.start_off; q.lt_off = (unsigned)L.lt_off;
-  q.ob_off = (unsigned)L.ob_off; q.bits_off = (unsigned)L.bits_off;
-  return launch_lds(k_viterbi<K, OBS, MODE>, dim3(a.B), dim3(kVitThreads), L.total, kLdsBudget, st, a, q);
-}
-
-template <int K, bool OBS>
-int launch_viterbi_mode(const ViterbiArgs& a, const VitLayout& L, bool vec, int mode, hipStream_t st) {
-  if (mode == 0) return launch_viterbi_k<K, OBS, 0>(a, L, vec, st);
-  if (mode == 1) return launch_viterbi_k<K, OBS, 1>(a, L, vec, st);
-  return launch_viterbi_k<K, OBS, 2>(a, L, vec, st);
+  const VitParams q{L.R, vec, (unsigned)L.start_off, (unsigned)L.lt_off, (unsigned)L.ob_off, (unsigned)L.bits_off};
+  return launch_lds(k_viterbi<K, OBS, MODE>, dim3(a.B), dim3(kAlnThreads), L.total, kLdsBudget, st, a, q);
 }
 
 template <bool OBS>
 int launch_viterbi_obs(const ViterbiArgs& a, const VitLayout& L, bool vec, int mode, hipStream_t st) {
-  switch (L.K) {
-    case 1: return launch_viterbi_mode<1, OBS>(a, L, vec, mode, st);
-    case 2: return launch_viterbi_mode<2, OBS>(a, L, vec, mode, st);
-    case 4: return launch_viterbi_mode<4, OBS>(a, L, vec, mode, st);
-    case 8: return launch_viterbi_mode<8, OBS>(a, L, vec, mode, st);
-    default: return launch_viterbi_mode<16, OBS>(a, L, vec, mode, st);
-  }
+  return aln_with_k(L.K, [&](auto Kc) {
+    constexpr int K = decltype(Kc)::value;
+    if (mode == 0) return launch_viterbi_k<K, OBS, 0>(a, L, vec, st);
+    if (mode == 1) return launch_viterbi_k<K, OBS, 1>(a, L, vec, st);
+    return launch_viterbi_k<K, OBS, 2>(a, L, vec, st);
+  });
 }
 
 }  // namespace
 
 size_t viterbi_workspace_bytes(int B, int T, int U) {
   if (vit_bits_fit(T, U)) return 0;
-  return (size_t)B * T * vit_k(U) * 8;
+  return (size_t)B * T * aln_k(U) * 8;
 }
 
 int launch_viterbi(const ViterbiArgs& a, hipStream_t st) {
-  if (a.B < 0 || a.T < 0 || a.U < 0 || (a.flags & ~SSNT_FLAG_TERMINAL_EMIT)) return SSNT_ERR_INVALID_ARG;
-  if (a.B == 0) return SSNT_OK;
-  if (!a.log_trans || !a.step_len || !a.pos_len || !a.log_prob) return SSNT_ERR_INVALID_ARG;
-  if (a.U > 1024) return SSNT_ERR_UNSUPPORTED;
-  if (!aligned_to(a.log_trans, 8) || !aligned_to(a.log_obs, 4)) return SSNT_ERR_UNSUPPORTED;
+  const int rc = aln_check_args(a.B, a.T, a.U, a.flags, a.log_trans && a.step_len && a.pos_len && a.log_prob,
+                                a.log_trans, a.log_obs);
+  if (rc != SSNT_OK || a.B == 0) return rc;
   const bool path = a.position || a.duration;
   const bool obs = a.log_obs != nullptr;
   const int U = a.U > 0 ? a.U : 1;  // (T == 0 or U == 0: every utterance is infeasible)
   const bool fit = a.T == 0 || a.U == 0 || vit_bits_fit(a.T, U);
-  if (path && !fit) {
-    const size_t need = viterbi_workspace_bytes(a.B, a.T, a.U);
-    if (!a.workspace || a.workspace_bytes < need || !aligned_to(a.workspace, 8)) return SSNT_ERR_WORKSPACE;
-  }
+  if (path && !fit && !aln_workspace_ok(a.workspace, a.workspace_bytes, viterbi_workspace_bytes(a.B, a.T, a.U)))
+    return SSNT_ERR_WORKSPACE;
   const int mode = !path ? 0 : fit ? 1 : 2;
   const bool vec = aligned_to(a.log_trans, 16) && U % 2 == 0;
   const VitLayout L = vit_pick(a.T, U, vec && !obs, obs, mode);

@@ -95,3 +95,29 @@ def test_unclear_share_of_the_gpu_cases():
     n, t = SC.unclear_share(SC.exponent_range())
     print(f"exponent range: {n} of {t} unclear")
     assert n < t
+
+
+# The LDS-to-workspace switch of the size query, from the library before the scaffold was shared
+# (csrc/align_dev.h): per number of samples, the largest T with a zero answer for each U, and the
+# bytes at T + 1 with B = 3.
+SWITCH_U = (1, 64, 65, 128, 129, 256, 257, 512, 513, 1024)
+SWITCH = {
+    1: ((1520, 1362, 2226, 2147, 306, 226, 753, 673, 368, 289),
+        (36504, 32712, 106896, 103104, 29472, 21792, 144768, 129408, 141696, 111360)),
+    2: ((760, 681, 1113, 1073, 153, 113, 120, 80, 56, 16),
+        (36528, 32736, 106944, 103104, 29568, 21888, 46464, 31104, 43776, 13056)),
+    16: ((95, 85, 139, 134, 19, 14, 15, 10, 7, 2),
+         (36864, 33024, 107520, 103680, 30720, 23040, 49152, 33792, 49152, 18432)),
+    64: ((23, 21, 34, 33, 4, 3, 3, 2, 1, 0),
+         (36864, 33792, 107520, 104448, 30720, 24576, 49152, 36864, 49152, 24576)),
+}
+
+
+@pytest.mark.parametrize("NS", sorted(SWITCH))
+def test_workspace_switch_points_are_pinned(NS):
+    from test_viterbi_ref import last_zero_T
+    from ssnt_tts_amd._lib import load
+    q = load().ssnt_sample_align_workspace_size  # dlopen only; the size query is host code
+    for U, T, nbytes in zip(SWITCH_U, *SWITCH[NS]):
+        assert last_zero_T(lambda t: q(3, t, U, NS)) == T, U
+        assert (T == 0 or q(3, T, U, NS) == 0) and q(3, T + 1, U, NS) == nbytes, U

@@ -92,3 +92,31 @@ def test_viterbi_entries_in_header_library_and_ctypes_table():
     assert big > 0 and big % 8 == 0
     import ssnt_tts_amd
     assert "ssnt_viterbi_align" in ssnt_tts_amd.__all__
+
+
+# The LDS-to-workspace switch of the size query, from the library before the scaffold was shared
+# (csrc/align_dev.h): the largest T with a zero answer per U, and the bytes at T + 1 with B = 3.
+SWITCH_U = (1, 64, 65, 128, 129, 256, 257, 512, 513, 1024)
+SWITCH_T = (13814, 13782, 2283, 2267, 653, 1501, 846, 830, 439, 423)
+SWITCH_BYTES = (331560, 330792, 109632, 108864, 62784, 144192, 162624, 159552, 168960, 162816)
+
+
+def last_zero_T(query):
+    """The largest T in [0, 65536) for which query(T) == 0 (0 if there is none), by bisection."""
+    if query(1) > 0:
+        return 0
+    lo, hi = 1, 1 << 16
+    assert query(hi) > 0
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if query(mid) == 0 else (lo, mid)
+    return lo
+
+
+def test_workspace_switch_points_are_pinned():
+    from ssnt_tts_amd._lib import load
+    q = load().ssnt_viterbi_align_workspace_size  # dlopen only; the size query is host arithmetic
+    for U, T, nbytes in zip(SWITCH_U, SWITCH_T, SWITCH_BYTES):
+        assert last_zero_T(lambda t: q(3, t, U)) == T, U
+        assert q(3, T, U) == 0 and q(3, T + 1, U) == nbytes, U
+    assert q(64, 2000, 400) == 8192000 and q(256, 200, 80) == 0
