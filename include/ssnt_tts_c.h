@@ -119,6 +119,10 @@ int ssnt_version(char *buf, size_t len);
  * Outputs: loss (B) = -ln Z; grad_trans (B,T,U,2) = d loss / d log_trans (NULL = skip);
  * grad_obs (B,T,U) = d loss / d log_obs (NULL = skip); log_alpha / log_beta (B,T,U) debug
  * outputs (NULL = skip). Cells outside (S_b,P_b) get grad 0 and log-alpha/beta -inf.
+ * Never read into a result, whatever they hold (NaN and +-inf included): log_trans and log_obs at
+ * steps >= S_b or positions >= P_b, the shift out of position P_b - 1, every entry of step
+ * S_b - 1 but the terminal emit at (S_b - 1, P_b - 1) -- that one too without
+ * SSNT_FLAG_TERMINAL_EMIT -- and the previous contents of the outputs and the workspace.
  * Device variant: all pointers are device pointers; `stream` is a hipStream_t (NULL = legacy
  * default); `workspace` must hold ssnt_fwd_bwd_workspace_size() bytes -- always take the size
  * from that query, never compute it: it is 0 (NULL workspace) when every row of the dispatched
@@ -158,7 +162,8 @@ int ssnt_fwd_bwd_sum_device(const float *log_trans, const float *log_obs, const 
  * skip; -inf outside the lattice). grad_trans / grad_obs and every rule as
  * ssnt_fwd_bwd_device (the same launch, the same kernel the shape dispatches; gradients
  * bit-identical). `workspace`: ssnt_fwd_bwd_debug64_workspace_size() bytes (the plain
- * workspace plus the state planes, 16 B per cell). Device pointers, asynchronous. New: the
+ * workspace plus the state planes, 16 B per cell). The input cells never read into a result
+ * are those of ssnt_fwd_bwd_device. Device pointers, asynchronous. New: the
  * reference has no forward-backward. */
 size_t ssnt_fwd_bwd_debug64_workspace_size(int batch, int max_steps, int max_pos);
 int ssnt_fwd_bwd_debug64_device(const float *log_trans, const float *log_obs, const int *step_len,
@@ -181,7 +186,8 @@ int ssnt_fwd_bwd(const float *log_trans, const float *log_obs, const int *step_l
  * (B,U) = the number of steps each position holds (0 for positions >= P_b; NULL = skip). An
  * infeasible utterance (S_b < P_b, S_b = 0, P_b = 0, log_prob = -inf, or a length beyond the
  * tensor, which also sets SSNT_ERR_BAD_LENGTH in `status`) gets log_prob -inf, positions -1 and
- * durations 0. -inf inputs are legal. max_pos > 1024 returns SSNT_ERR_UNSUPPORTED. `workspace`
+ * durations 0. -inf inputs are legal; the input cells ssnt_fwd_bwd_device never reads into a result
+ * are never read into one here. max_pos > 1024 returns SSNT_ERR_UNSUPPORTED. `workspace`
  * holds ssnt_viterbi_align_workspace_size() bytes: 0 (NULL workspace) while the backpointer bits
  * of one utterance fit LDS; with position and duration both NULL no backpointers are kept and
  * no workspace is needed. Device pointers, asynchronous on `stream` (a hipStream_t). New: the
@@ -207,9 +213,10 @@ int ssnt_viterbi_align_device(const float *log_trans, const float *log_obs, cons
  * (B, num_samples, T) and duration (B, num_samples, U) as ssnt_viterbi_align_device, per sample
  * (NULL = skip). An infeasible utterance (S_b < P_b, S_b = 0, P_b = 0, alpha[S_b-1][P_b-1] = 0, or
  * a length beyond the tensor, which also sets SSNT_ERR_BAD_LENGTH in `status`) gets log_prob
- * -inf, positions -1 and durations 0 for every sample. -inf inputs are legal. max_pos > 1024
- * returns SSNT_ERR_UNSUPPORTED, num_samples outside [1, 64] SSNT_ERR_INVALID_ARG. `workspace`
- * holds ssnt_sample_align_workspace_size() bytes: 0 (NULL workspace) while the decision bits of
+ * -inf, positions -1 and durations 0 for every sample. -inf inputs are legal; the log_trans and
+ * log_obs cells ssnt_fwd_bwd_device never reads into a result are never read into one here.
+ * max_pos > 1024 returns SSNT_ERR_UNSUPPORTED, num_samples outside [1, 64]
+ * SSNT_ERR_INVALID_ARG. `workspace` holds ssnt_sample_align_workspace_size() bytes: 0 (NULL workspace) while the decision bits of
  * one utterance (num_samples * T words per lane slot) fit LDS; the bits are needed for log_prob
  * too, so the workspace does not depend on which outputs are requested. Device pointers,
  * asynchronous on `stream`. New: the reference has no sampler. */
@@ -229,8 +236,10 @@ int ssnt_sample_align_device(const float *log_trans, const float *log_obs, const
  * Outputs: loss (B) = -ln Z, Z = sum over every admissible class sequence of its probability
  * (+inf when none, 0 with SSNT_FLAG_ZERO_INFINITY); grad (B,T,D) = d loss / d logits = minus
  * the class posteriors (NULL = skip); log_alpha / log_beta (B,T+1,max_total+1) debug rows
- * (NULL = skip). `workspace` holds ssnt_v2_fwd_bwd_workspace_size() bytes. Device pointers,
- * asynchronous on `stream`; a negative duration sets SSNT_ERR_BAD_INDEX in `status`. */
+ * (NULL = skip). Never read into a result, whatever they hold: logits rows at steps >= I_b, and
+ * column zero_duration_id when allow_skip is false; grad is 0 there, and rows beyond I_b of the
+ * debug outputs are -inf. `workspace` holds ssnt_v2_fwd_bwd_workspace_size() bytes. Device
+ * pointers, asynchronous on `stream`; a negative duration sets SSNT_ERR_BAD_INDEX in `status`. */
 size_t ssnt_v2_fwd_bwd_workspace_size(int batch, int max_steps, int max_total, bool test_mode);
 int ssnt_v2_fwd_bwd_device(const float *logits, const int *duration_table, const int *input_length,
                            const int *output_length, int batch, int max_steps,
@@ -250,7 +259,8 @@ int ssnt_v2_fwd_bwd_device(const float *logits, const int *duration_table, const
  * = 0, band mode with O_b > max_total, log_prob = -inf, a length outside the tensor, which also
  * sets SSNT_ERR_BAD_LENGTH in `status`, or a negative duration, which sets SSNT_ERR_BAD_INDEX)
  * gets log_prob -inf, classes -1, durations 0 and total -1. -inf logits are legal; +inf is not
- * clamped. Limits as F4: duration_class_size > 64 and a row beyond LDS return
+ * clamped. Logits rows at steps >= I_b, and column zero_duration_id when allow_skip is false, are
+ * never read into a result. Limits as F4: duration_class_size > 64 and a row beyond LDS return
  * SSNT_ERR_UNSUPPORTED, max_total outside [0, 1<<24] SSNT_ERR_INVALID_ARG. `workspace` holds
  * ssnt_v2_viterbi_align_workspace_size() bytes: 0 (NULL workspace) while the backpointer bytes
  * of one utterance fit LDS; with duration_class and duration both NULL no backpointers are kept

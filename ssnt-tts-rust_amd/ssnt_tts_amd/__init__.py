@@ -507,7 +507,7 @@ def ssnt_lattice_loss(log_trans, step_len, pos_len, log_obs=None, terminal_emit=
 # ----------------------------------------------------------------------------------------------
 def v2_fwd_bwd(logits, duration_table, input_length, output_length, zero_duration_id, *,
                allow_skip=False, test_mode=False, max_total=None, zero_infinity=False,
-               need_grad=True, debug=False, check=False):
+               need_grad=True, debug=False, check=False, out=None):
     """Forward-backward over the v2 duration-class lattice: the sum over every class sequence the
     v2 decode could keep (src/v2.rs:94-166 move rules) of its probability.
 
@@ -515,7 +515,8 @@ def v2_fwd_bwd(logits, duration_table, input_length, output_length, zero_duratio
     input_length / output_length (B,). ``max_total`` bounds the state totals (default
     max(output_length), read back from the device). Returns ``loss`` (B,) = -ln Z, ``grad``
     (B,T,D) = d loss / d logits (= minus the class posteriors), and with ``debug`` the rows
-    ``log_alpha`` / ``log_beta`` (B,T+1,max_total+1)."""
+    ``log_alpha`` / ``log_beta`` (B,T+1,max_total+1). Rows of ``grad`` at steps >= I_b are 0.
+    ``out`` may pass preallocated tensors under the same keys."""
     lib = load(require_gpu=True)
     lg = _dev(logits, torch.float32, "logits")
     dev = lg.device
@@ -526,13 +527,19 @@ def v2_fwd_bwd(logits, duration_table, input_length, output_length, zero_duratio
     if max_total is None:
         max_total = int(ol.max().item()) if B > 0 else 0
     X = int(max_total) + 1
-    loss = torch.empty(B, dtype=torch.float32, device=dev)
-    grad = torch.empty((B, T, D), dtype=torch.float32, device=dev) if need_grad else None
-    la = torch.empty((B, T + 1, X), dtype=torch.float32, device=dev) if debug else None
-    lb = torch.empty((B, T + 1, X), dtype=torch.float32, device=dev) if debug else None
+    out = dict(out or {})
+    f32 = {"dtype": torch.float32, "name": "float32"}
+    loss = _buf(out, dev, "loss", (B,), **f32)
+    grad = _buf(out, dev, "grad", (B, T, D), want=need_grad, **f32)
+    la = _buf(out, dev, "log_alpha", (B, T + 1, X), want=debug, **f32)
+    lb = _buf(out, dev, "log_beta", (B, T + 1, X), want=debug, **f32)
     wsb = int(lib.ssnt_v2_fwd_bwd_workspace_size(B, T, int(max_total), bool(test_mode)))
     ws = _workspace(dev, wsb)
-    st = _status(dev)
+    st = out.get("status")
+    if st is None:
+        st = _status(dev)
+    else:
+        st.zero_()
     rc = lib.ssnt_v2_fwd_bwd_device(_p(lg), _p(table), _p(il), _p(ol), B, T, D, int(max_total),
                                     int(zero_duration_id), bool(allow_skip), bool(test_mode),
                                     FLAG_ZERO_INFINITY if zero_infinity else 0, _p(loss),

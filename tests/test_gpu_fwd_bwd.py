@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from loss_sum_ref import wave_order_sum as _wave_order_sum
+
 pytestmark = pytest.mark.gpu
 
 F_TERM, F_ZINF = 1, 2
@@ -440,19 +442,22 @@ def test_autograd_function(gpu, oracle):
     assert np.array_equal(loss.detach().cpu().numpy(), o["loss"])
     want = o["grad"] * np.array([1.0, 2.0, 0.5], np.float32)[:, None, None, None]
     assert np.array_equal(x.grad.cpu().numpy(), want)
-
-
-def _wave_order_sum(loss):
-    """The library's fixed summation order: 64 lane-strided f32 partial sums, then an xor
-    butterfly (lattice_dev.h wave_loss_sum)."""
-    acc = np.zeros(64, np.float32)
-    for i, v in enumerate(np.asarray(loss, np.float32)):
-        acc[i % 64] = np.float32(acc[i % 64] + v)
-    off = 32
-    while off >= 1:
-        acc = (acc + acc[np.arange(64) ^ off]).astype(np.float32)
-        off //= 2
-    return acc[0]
+    # the same batch as a training step brings it: padded, and the padding is NaN (log_softmax of
+    # a fully masked row). The loss and the gradients are those of the clean batch: finite
+    # everywhere, exactly 0 in the padding
+    pad = np.zeros(lt.shape[:3], bool)
+    for b, (s, p) in enumerate(zip([20, 15, 9], [8, 8, 4])):
+        pad[b, s:], pad[b, :, p:] = True, True
+    assert pad.any()
+    ltn = lt.copy()
+    ltn[pad] = np.nan
+    xn = torch.from_numpy(ltn).to(dev).requires_grad_(True)
+    lossn = gpu.ssnt_lattice_loss(xn, S, P)
+    (lossn * w).sum().backward()
+    gn = xn.grad.cpu().numpy()
+    assert np.array_equal(lossn.detach().cpu().numpy(), o["loss"])
+    assert np.all(np.isfinite(gn)) and not gn[pad].any()
+    assert np.array_equal(gn, want)
 
 
 @pytest.mark.parametrize("B", [1, 70, 256])

@@ -118,7 +118,26 @@ def test_autograd(gpu, oracle):
     o = oracle.v2_fwd_bwd(logits, table, I, O, int(O.max()), 0, True, False,
                           flags=oracle.FLAG_ZERO_INFINITY)
     assert np.array_equal(loss.detach().cpu().numpy(), o["loss"])
-    assert np.array_equal(x.grad.cpu().numpy(), o["grad"] * np.array([1.0, 0.5, 2.0], np.float32)[:, None, None])
+    want = o["grad"] * np.array([1.0, 0.5, 2.0], np.float32)[:, None, None]
+    assert np.array_equal(x.grad.cpu().numpy(), want)
+    # the same batch padded with NaN rows beyond each input length (log_softmax of a masked row):
+    # the loss and the gradients of the clean batch, finite everywhere, exactly 0 in the padding
+    I2 = np.minimum(I, [7, 5, 3]).astype(np.int32)
+    O2 = np.minimum(O, 3 * I2).astype(np.int32)
+    pad = np.arange(7)[None, :] >= I2[:, None]
+    assert pad.any()
+    mt = int(O.max())
+    o2 = oracle.v2_fwd_bwd(logits, table, I2, O2, mt, 0, True, False, flags=oracle.FLAG_ZERO_INFINITY)
+    lgn = logits.copy()
+    lgn[pad] = np.nan
+    xn = torch.from_numpy(lgn).to(DEV).requires_grad_(True)
+    lossn = gpu.v2_duration_loss(xn, torch.from_numpy(table).to(DEV), torch.from_numpy(I2).to(DEV),
+                                 torch.from_numpy(O2).to(DEV), 0, True, False, mt, True)
+    (lossn * w).sum().backward()
+    gn = xn.grad.cpu().numpy()
+    assert np.array_equal(lossn.detach().cpu().numpy(), o2["loss"])
+    assert np.all(np.isfinite(gn)) and not gn[pad].any()
+    assert np.array_equal(gn, o2["grad"] * np.array([1.0, 0.5, 2.0], np.float32)[:, None, None])
 
 
 def test_negative_duration_is_reported(gpu):

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import f4_cases
+import guarded as G
 import v2_viterbi_ref as VR
 
 pytestmark = pytest.mark.gpu
@@ -213,28 +214,36 @@ def _switch_I(gpu, max_total, test_mode):
 
 
 def _poisoned(gpu, logits, table, I, O, mt, test_mode):
-    """The C entry with a 0xFF-filled workspace of exactly the queried size."""
+    """The C entry with a workspace of exactly the queried size in a guarded arena (guarded.py),
+    filled with 0xFF, with 0x00, and left as a finished run of other logits of the same shape
+    wrote it: the results of the three runs (the guards are checked after each)."""
     lib = gpu.load()
     B, T, D = logits.shape
     need = int(lib.ssnt_v2_viterbi_align_workspace_size(B, T, mt, test_mode))
     assert need > 0
-    ws = torch.full((need,), 0xFF, dtype=torch.uint8, device=DEV)
-    x, tb = _t(logits), _t(np.asarray(table), torch.int32)
-    il, ol = _t(np.asarray(I), torch.int32), _t(np.asarray(O), torch.int32)
-    lp = torch.empty(B, dtype=torch.float32, device=DEV)
-    cls = torch.empty((B, T), dtype=torch.int32, device=DEV)
-    dur = torch.empty((B, T), dtype=torch.int32, device=DEV)
-    tot = torch.empty(B, dtype=torch.int32, device=DEV)
-    st = torch.zeros(1, dtype=torch.int32, device=DEV)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    rc = lib.ssnt_v2_viterbi_align_device(vp(x), vp(tb), vp(il), vp(ol), B, T, D, mt, 0, True, test_mode,
-                                          vp(lp), vp(cls), vp(dur), vp(tot), vp(ws), need, vp(st),
-                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0
-    torch.cuda.synchronize()
-    assert int(st.item()) == 0
-    return {"log_prob": lp.cpu().numpy(), "duration_class": cls.cpu().numpy(),
-            "duration": dur.cpu().numpy(), "total": tot.cpu().numpy()}
+    f32, i32 = torch.float32, torch.int32
+    arena, v = G.lay_out(DEV, {"lg": ((B, T, D), f32), "table": ((D,), i32), "il": ((B,), i32),
+                               "ol": ((B,), i32), "log_prob": ((B,), f32), "duration_class": ((B, T), i32),
+                               "duration": ((B, T), i32), "total": ((B,), i32), "status": ((1,), i32),
+                               "ws": ((need,), torch.uint8)})
+    for k, a in (("table", table), ("il", I), ("ol", O)):
+        G.put(v[k], np.asarray(a, np.int32))
+    res = []
+    for fill in (0xFF, 0x00, "stale"):
+        for x in ([logits] if fill != "stale" else [logits[::-1, ::-1], logits]):  # stale: other logits first
+            G.put(v["lg"], np.ascontiguousarray(x, np.float32))
+            if fill != "stale":
+                G.fill_bytes(v["ws"], fill)
+            v["status"].zero_()
+            rc = G.call(lib, "ssnt_v2_viterbi_align_device", v["lg"], v["table"], v["il"], v["ol"], B, T, D,
+                        int(mt), 0, True, bool(test_mode), v["log_prob"], v["duration_class"], v["duration"],
+                        v["total"], v["ws"], need, v["status"], torch.cuda.current_stream().cuda_stream)
+            assert rc == 0
+            torch.cuda.synchronize()
+            assert int(v["status"].item()) == 0
+            arena.check()
+        res.append({k: G.get(v[k]) for k in ("log_prob", "duration_class", "duration", "total")})
+    return res
 
 
 @pytest.mark.parametrize("test_mode,mt", [(True, 300), (False, 2000)], ids=["test_mode", "band"])
@@ -259,7 +268,8 @@ def test_lds_to_workspace_switch(gpu, oracle, test_mode, mt):
         assert np.all(ref["log_prob"] > -np.inf)
         _same(_run(gpu, logits, table, I, O, mt, 0, True, test_mode, check=True), ref, T)
         if q(B, T, mt, test_mode) > 0:
-            _same(_poisoned(gpu, logits, table, I, O, mt, test_mode), ref, (T, "poisoned"))
+            for g in _poisoned(gpu, logits, table, I, O, mt, test_mode):
+                _same(g, ref, (T, "poisoned"))
     assert q(B, Il, mt, test_mode) == 0 and q(B, Il + 1, mt, test_mode) > 0
 
 

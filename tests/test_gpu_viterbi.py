@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import guarded as G
 import lattice_ref
 import viterbi_ref as VR
 
@@ -139,25 +140,35 @@ def _switch_T(gpu, U):
 
 
 def _poisoned(gpu, lt, S, P):
-    """The C entry with a 0xFF-filled workspace of exactly the queried size."""
+    """The C entry with a workspace of exactly the queried size in a guarded arena (guarded.py),
+    filled with 0xFF, with 0x00, and left as a finished run of another lattice of the same shape
+    wrote it: the results of the three runs (the guards are checked after each)."""
     lib = gpu.load()
     B, T, U, _ = lt.shape
     need = int(lib.ssnt_viterbi_align_workspace_size(B, T, U))
     assert need > 0
-    ws = torch.full((need,), 0xFF, dtype=torch.uint8, device=DEV)
-    x, s, p = _t(lt), _t(np.asarray(S), torch.int32), _t(np.asarray(P), torch.int32)
-    lp = torch.empty(B, dtype=torch.float32, device=DEV)
-    pos = torch.empty((B, T), dtype=torch.int32, device=DEV)
-    dur = torch.empty((B, U), dtype=torch.int32, device=DEV)
-    st = torch.zeros(1, dtype=torch.int32, device=DEV)
-    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    rc = lib.ssnt_viterbi_align_device(vp(x), None, vp(s), vp(p), B, T, U, 1, vp(lp), vp(pos), vp(dur),
-                                       vp(ws), need, vp(st),
-                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0
-    torch.cuda.synchronize()
-    assert int(st.item()) == 0
-    return {"log_prob": lp.cpu().numpy(), "position": pos.cpu().numpy(), "duration": dur.cpu().numpy()}
+    f32, i32 = torch.float32, torch.int32
+    arena, v = G.lay_out(DEV, {"lt": ((B, T, U, 2), f32), "sl": ((B,), i32), "pl": ((B,), i32),
+                               "log_prob": ((B,), f32), "position": ((B, T), i32), "duration": ((B, U), i32),
+                               "status": ((1,), i32), "ws": ((need,), torch.uint8)})
+    G.put(v["sl"], np.asarray(S, np.int32))
+    G.put(v["pl"], np.asarray(P, np.int32))
+    res = []
+    for fill in (0xFF, 0x00, "stale"):
+        for x in ([lt] if fill != "stale" else [lt[::-1, ::-1], lt]):  # stale: another lattice first
+            G.put(v["lt"], np.ascontiguousarray(x))
+            if fill != "stale":
+                G.fill_bytes(v["ws"], fill)
+            v["status"].zero_()
+            rc = G.call(lib, "ssnt_viterbi_align_device", v["lt"], None, v["sl"], v["pl"], B, T, U, 1,
+                        v["log_prob"], v["position"], v["duration"], v["ws"], need, v["status"],
+                        torch.cuda.current_stream().cuda_stream)
+            assert rc == 0
+            torch.cuda.synchronize()
+            assert int(v["status"].item()) == 0
+            arena.check()
+        res.append({k: G.get(v[k]) for k in ("log_prob", "position", "duration")})
+    return res
 
 
 @pytest.mark.parametrize("U", [130, 400])
@@ -171,7 +182,8 @@ def test_lds_to_workspace_switch(gpu, U):
         ref = VR.dp(lt, S, P)
         _same(_run(gpu, lt, S, P, check=True), ref, T)
         if lib.ssnt_viterbi_align_workspace_size(B, T, U) > 0:
-            _same(_poisoned(gpu, lt, S, P), ref, (T, "poisoned"))
+            for g in _poisoned(gpu, lt, S, P):
+                _same(g, ref, (T, "poisoned"))
     assert lib.ssnt_viterbi_align_workspace_size(B, Tl, U) == 0
     assert lib.ssnt_viterbi_align_workspace_size(B, Tl + 1, U) > 0
 
@@ -183,7 +195,8 @@ def test_long_shapes(gpu, shape):
     S, P = [T, T - 37], [U, U - 11]
     ref = VR.dp(lt, S, P)
     _same(_run(gpu, lt, S, P, check=True), ref)
-    _same(_poisoned(gpu, lt, S, P), ref, "poisoned")
+    for g in _poisoned(gpu, lt, S, P):
+        _same(g, ref, "poisoned")
 
 
 # ---- 6. headline shape -----------------------------------------------------------------------
