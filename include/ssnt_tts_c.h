@@ -275,6 +275,39 @@ int ssnt_v2_viterbi_align_device(const float *logits, const int *duration_table,
                                  void *workspace, size_t workspace_bytes, int *status,
                                  void *stream);
 
+/* ---- duration paths drawn from the posterior of the v2 duration-class lattice (DESIGN.md 2.5,
+ * 5.9). Forward filter, backward sample on F4's lattice (same inputs, states, windows and class
+ * rule as ssnt_v2_fwd_bwd_device): the forward rows are F4's alpha, bit for bit; walking back from
+ * the final total, each step draws its class among the D <= 64 terms entering the cell, in class
+ * order, with one uniform number. `uniform` (B,K,T+1) is the randomness, K = num_samples in
+ * [1, 64]: [b,k,t] chooses the class of step t, [b,k,T] the final total (band mode: forced to
+ * O_b); each number is clamped to [0, 1 - 2^-24], NaN counts as 0. The library holds no generator
+ * state: a call is a pure function of its arguments, and every output is an admissible class
+ * sequence whatever `uniform` holds. log_prob (B,K) = the drawn sequence's log-probability, the
+ * sequential f32 sum of logits[b,t,class_t] over t = 0..I_b-1 from 0.0f; duration_class (B,K,T)
+ * (-1 for steps >= I_b); duration (B,K,T) = duration_table[class] (0 for steps >= I_b); total
+ * (B,K) = the drawn final total. Each of the three may be NULL. An utterance with no admissible
+ * path (I_b = 0, band mode with O_b > max_total, Z = 0, a length outside the tensor, which also
+ * sets SSNT_ERR_BAD_LENGTH in `status`, or a negative duration, which sets SSNT_ERR_BAD_INDEX)
+ * gets log_prob -inf, classes -1, durations 0 and total -1 for every sample. -inf logits are
+ * legal; NaN and +inf are unspecified in value. Logits rows at steps >= I_b, and column
+ * zero_duration_id when allow_skip is false, are never read into a result. Limits as F4:
+ * duration_class_size > 64 and a row beyond LDS return SSNT_ERR_UNSUPPORTED; num_samples outside
+ * [1, 64] and max_total outside [0, 1<<24] SSNT_ERR_INVALID_ARG. `workspace` holds
+ * ssnt_v2_sample_align_workspace_size() bytes, 8-byte aligned (F4's forward rows and Z; the same
+ * whichever outputs are requested); a missing, short or misaligned one returns
+ * SSNT_ERR_WORKSPACE. A refused call writes nothing. Device pointers, asynchronous on `stream`
+ * (two launches). New: the reference has no sampler. */
+size_t ssnt_v2_sample_align_workspace_size(int batch, int max_steps, int max_total, bool test_mode,
+                                           int num_samples);
+int ssnt_v2_sample_align_device(const float *logits, const int *duration_table,
+                                const int *input_length, const int *output_length,
+                                const float *uniform, int batch, int max_steps,
+                                int duration_class_size, int max_total, int zero_duration_id,
+                                bool allow_skip, bool test_mode, int num_samples, float *log_prob,
+                                int *duration_class, int *duration, int *total, void *workspace,
+                                size_t workspace_bytes, int *status, void *stream);
+
 /* ---- batched decode steps, device pointers (the reference FFI fixes v1 to B=1,
  * ssnt_tts_c/src/lib.rs:13; its Rust API takes B, src/lib.rs:121). max_beam_width = beam_width
  * as in every reference call site (ssnt_tts_c/src/lib.rs:82,217,342). ---- */

@@ -31,6 +31,11 @@ int ssnt_fwd_bwd_wide_split(int mode);
 /* segmented kernel, split form: the downstream workgroup's first compute wave sleeps `sleeps`
  * x s_sleep 127 per block (0 default), so the receiver runs a whole ring ahead (race test) */
 int ssnt_fwd_bwd_wide_lag(int sleeps);
+/* v2 posterior sampler: steps per memory round trip of the walk (0 by dmax, 1 one gather per
+ * step, 2, 4; the deeper forms apply while steps * dmax <= 63) and the launches that run (bit 0
+ * the forward sweep, bit 1 the walk; 3 default: timing one launch over a workspace an earlier full
+ * call left) */
+int ssnt_v2_sample_align_form(int cone, int launches);
 /* per-step reference symbols: host staging 0 copies / 1 zero-copy; completion 0 stream
  * synchronise / 1 hipStreamWriteValue32 word / 2 flag kernel; both return the previous mode */
 int ssnt_set_host_staging(int mode);

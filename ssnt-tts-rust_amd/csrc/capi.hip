@@ -701,6 +701,7 @@ int ssnt_fwd_bwd_wide_split(int mode) { return set_fwd_bwd_wide_split(mode); }
 // the split form's downstream first compute wave idles `sleeps` x s_sleep 127 per block, so the
 // receiver proxy runs a whole ring ahead of it (tests/test_gpu_fwd_bwd.py hand-off race test)
 int ssnt_fwd_bwd_wide_lag(int sleeps) { return set_fwd_bwd_wide_lag(sleeps); }
+int ssnt_v2_sample_align_form(int cone, int launches) { return set_v2_sample_form(cone, launches); }
 
 // Per-step symbol latency breakdown (tools/bench_step_symbols.py).
 // enable = 1 resets and starts the calling thread's phase clock; 0 stops it and writes the mean
@@ -869,6 +870,30 @@ int ssnt_v2_viterbi_align_device(const float* logits, const int* duration_table,
   a.duration = duration; a.total = total; a.workspace = workspace;
   a.workspace_bytes = workspace_bytes; a.status = status;
   return launch_v2_viterbi(a, as_stream(stream));
+}
+
+size_t ssnt_v2_sample_align_workspace_size(int batch, int max_steps, int max_total, bool test_mode,
+                                           int num_samples) {
+  if (max_total < 0 || max_total > (1 << 24) || num_samples < 1 || num_samples > 64) return 0;
+  return v2_sample_workspace_bytes(batch, max_steps, max_total, test_mode);
+}
+
+int ssnt_v2_sample_align_device(const float* logits, const int* duration_table,
+                                const int* input_length, const int* output_length,
+                                const float* uniform, int batch, int max_steps,
+                                int duration_class_size, int max_total, int zero_duration_id,
+                                bool allow_skip, bool test_mode, int num_samples, float* log_prob,
+                                int* duration_class, int* duration, int* total, void* workspace,
+                                size_t workspace_bytes, int* status, void* stream) {
+  if (max_total < 0 || max_total > (1 << 24)) return SSNT_ERR_INVALID_ARG;
+  V2SampleArgs a{};
+  a.logits = logits; a.table = duration_table; a.input_length = input_length;
+  a.output_length = output_length; a.uniform = uniform; a.B = batch; a.Imax = max_steps;
+  a.D = duration_class_size; a.X = max_total + 1; a.NS = num_samples; a.zid = zero_duration_id;
+  a.allow_skip = allow_skip; a.test_mode = test_mode; a.log_prob = log_prob;
+  a.duration_class = duration_class; a.duration = duration; a.total = total;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  return launch_v2_sample_align(a, as_stream(stream));
 }
 
 int ssnt_fwd_bwd(const float* log_trans, const float* log_obs, const int* step_len,

@@ -136,10 +136,16 @@ struct V2FwdBwdArgs {
   size_t workspace_bytes;
   int Wcap;                  // set by the launcher
   int chunk;                 // set by the launcher
+  bool fwd_only;             // set by the launcher: alpha rows and Z only (workspace: rows | Z)
   int* status;
 };
 size_t v2_fwd_bwd_workspace_bytes(int B, int Imax, int max_total, bool test_mode);
 int launch_v2_fwd_bwd(const V2FwdBwdArgs& a, hipStream_t stream);
+// F4's forward sweep alone, for the sampler: alpha rows 0..I and Z into a workspace of
+// v2_fwd_only_workspace_bytes() (loss may be null; grad and the debug rows are ignored).
+// launch == false: F4's refusals only, nothing launched.
+size_t v2_fwd_only_workspace_bytes(int B, int Imax, int max_total, bool test_mode);
+int launch_v2_fwd_only(const V2FwdBwdArgs& a, bool launch, hipStream_t stream);
 
 // ---- exact best duration path on the v2 lattice (v2_viterbi.hip) ----
 struct V2ViterbiArgs {
@@ -161,6 +167,33 @@ struct V2ViterbiArgs {
 };
 size_t v2_viterbi_workspace_bytes(int B, int Imax, int max_total, bool test_mode);
 int launch_v2_viterbi(const V2ViterbiArgs& a, hipStream_t stream);
+
+// ---- duration paths drawn from the posterior of the v2 lattice (v2_sample_align.hip) ----
+struct V2SampleArgs {
+  const float* logits;       // (B, Imax, D) per-step class log-probs
+  const int* table;          // (D) duration_table, >= 0
+  const int* input_length;   // (B) I_b <= Imax
+  const int* output_length;  // (B) O_b
+  const float* uniform;      // (B, NS, Imax+1): the random input; [.., t] step t's class, [.., Imax] the total
+  int B, Imax, D, X, NS;     // X = max_total + 1 totals per row; NS: samples per utterance, 1..64
+  int zid;                   // zero_duration_id
+  bool allow_skip, test_mode;
+  float* log_prob;           // (B, NS)
+  int* duration_class;       // (B, NS, Imax) or null
+  int* duration;             // (B, NS, Imax) or null
+  int* total;                // (B, NS) or null
+  void* workspace;           // F4's alpha rows and Z
+  size_t workspace_bytes;
+  int Wcap;                  // set by the launcher
+  int* status;
+};
+size_t v2_sample_workspace_bytes(int B, int Imax, int max_total, bool test_mode);
+int launch_v2_sample_align(const V2SampleArgs& a, hipStream_t stream);
+#ifdef SSNT_AB
+// steps per memory round trip of the walk (0 auto, 1, 2, 4) and which launches run (bit 0 the
+// forward sweep, bit 1 the walk; 3 default)
+int set_v2_sample_form(int cone, int launches);
+#endif
 
 // ---- beam-search decode (decode.hip) ----
 enum class Variant : int { V1 = 0, V2 = 1, Tone = 2 };

@@ -25,6 +25,8 @@
 // i % 4, every class of a wave accumulated in one pass over the destination totals (lane
 // partial x mod 64, the oracle's order), one butterfly per class (DPP quad/mirror moves, a
 // swizzle, one bpermute) -- and the debug beta row. Fully parallel (B * I workgroups).
+// launch_v2_fwd_only runs the forward workgroups of launch 1 alone (alpha rows and Z, no loss, into
+// a workspace without the beta rows): the forward filter of v2_sample_align.hip.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 
@@ -161,13 +163,14 @@ __device__ __forceinline__ int f4_reduce_classes(xf (&acc)[N], int lane, int cls
 }
 
 // workspace: alpha rows [B][Imax+1][Wc] | beta rows [B][Imax+1][Wc] | Z [B]
+// (forward only, launch_v2_fwd_only: alpha rows | Z)
 struct F4Ws {
   xf *alpha, *beta, *z;
 };
 __device__ __forceinline__ F4Ws f4_ws(const V2FwdBwdArgs& a) {
   xf* base = reinterpret_cast<xf*>(a.workspace);
   const size_t rows = (size_t)a.B * (a.Imax + 1) * a.Wcap;
-  return F4Ws{base, base + rows, base + 2 * rows};
+  return F4Ws{base, base + rows, base + (a.fwd_only ? rows : 2 * rows)};
 }
 
 // sweep steps per staged chunk of class weights
@@ -272,7 +275,7 @@ __device__ __forceinline__ void f4_sweep(const V2FwdBwdArgs& a, unsigned char* s
     if (hi - lo + 1 > Wc) {  // host sizing bug: report, poison the loss (uniform branch)
       if (tid == 0) {
         if (a.status) atomicOr(a.status, kStatusBadLength);
-        if (FWD) a.loss[b] = __builtin_nanf("");
+        if (FWD && a.loss) a.loss[b] = __builtin_nanf("");
       }
       return false;
     }
@@ -343,7 +346,7 @@ __device__ __forceinline__ void f4_sweep(const V2FwdBwdArgs& a, unsigned char* s
     acc = f4_butterfly(acc);
     if (lane == 0) {
       W.z[b] = acc;
-      a.loss[b] = acc.m == 0.0f ? inf_loss : 0.0f - xf_log(acc);
+      if (a.loss) a.loss[b] = acc.m == 0.0f ? inf_loss : 0.0f - xf_log(acc);
     }
   }
 }
@@ -361,7 +364,7 @@ __global__ __launch_bounds__(kF4Threads) void k_f4_sweep(V2FwdBwdArgs a) {
   if (!f4_setup(a, b, dur, u, fwd)) {
     if (fwd) {
       const float inf_loss = (a.flags & SSNT_FLAG_ZERO_INFINITY) ? 0.0f : __builtin_inff();
-      if (tid == 0) a.loss[b] = inf_loss;
+      if (tid == 0 && a.loss) a.loss[b] = inf_loss;
       if (a.log_alpha)
         for (int r = 0; r <= a.Imax; ++r)
           f4_log_row(a.log_alpha + b * (size_t)(a.Imax + 1) * a.X + (size_t)r * a.X, nullptr, 0, -1, a.X);
@@ -503,18 +506,25 @@ size_t v2_fwd_bwd_workspace_bytes(int B, int Imax, int max_total, bool test_mode
   return (2 * (size_t)B * (Imax + 1) * v2_fwd_bwd_wcap(max_total, test_mode) + B) * sizeof(xf);
 }
 
+size_t v2_fwd_only_workspace_bytes(int B, int Imax, int max_total, bool test_mode) {
+  if (B <= 0 || Imax <= 0 || max_total < 0) return 0;
+  return ((size_t)B * (Imax + 1) * v2_fwd_bwd_wcap(max_total, test_mode) + B) * sizeof(xf);
+}
+
+// the sweep launch: both directions, or (fwd_only) the alpha workgroups alone -- blockIdx.y == 0
 template <int DC>
 int launch_f4(const V2FwdBwdArgs& a, size_t lds, size_t glds, hipStream_t st) {
   // (each launch raises its own attribute to what it asks for)
-  const int rc = launch_lds(k_f4_sweep<DC>, dim3(a.B, 2), dim3(kF4Threads), lds, lds, st, a);
-  if (rc != SSNT_OK || (!a.grad && !a.log_beta)) return rc;
+  const int rc = launch_lds(k_f4_sweep<DC>, dim3(a.B, a.fwd_only ? 1 : 2), dim3(kF4Threads), lds, lds, st, a);
+  if (rc != SSNT_OK || a.fwd_only || (!a.grad && !a.log_beta)) return rc;
   return launch_lds(k_f4_grad<DC>, dim3(a.B, a.Imax + 1), dim3(f4_grad_threads<DC>()), glds, glds, st, a);
 }
 
-int launch_v2_fwd_bwd(const V2FwdBwdArgs& in, hipStream_t st) {
-  V2FwdBwdArgs a = in;
+namespace {
+// what both entries refuse, in this order; sets Wcap / chunk and the LDS of the two launches
+int f4_plan(V2FwdBwdArgs& a, bool need_loss, size_t& lds, size_t& glds) {
   if (a.B < 0 || a.Imax <= 0 || a.D <= 0 || a.X <= 0 || !a.logits || !a.table || !a.input_length ||
-      !a.output_length || !a.loss)
+      !a.output_length || (need_loss && !a.loss))
     return SSNT_ERR_INVALID_ARG;
   if (a.B == 0) return SSNT_OK;
   if (a.D > 64) return SSNT_ERR_UNSUPPORTED;  // cell sums unrolled over <= 64 classes
@@ -523,21 +533,47 @@ int launch_v2_fwd_bwd(const V2FwdBwdArgs& in, hipStream_t st) {
   const int Dp = a.D <= 8 ? 8 : a.D <= 16 ? 16 : a.D <= 32 ? 32 : 64;  // = DC
   const size_t head = (size_t)((Dp * 4 + 15) & ~15);
   a.chunk = Dp <= 32 ? 64 : 32;  // = f4_chunk<DC>()
-  const size_t lds = head + 2 * (size_t)a.chunk * Dp * sizeof(xf) +
-                     2 * ((size_t)a.Wcap + 2 * kF4Pad + 2) * sizeof(xf);
-  const size_t glds = head + (2 * (size_t)a.Wcap + 2 * kF4Pad + 1) * sizeof(xf);
+  lds = head + 2 * (size_t)a.chunk * Dp * sizeof(xf) + 2 * ((size_t)a.Wcap + 2 * kF4Pad + 2) * sizeof(xf);
+  glds = head + (2 * (size_t)a.Wcap + 2 * kF4Pad + 1) * sizeof(xf);
   if (lds > 160 * 1024 - 1024 || glds > 160 * 1024 - 1024) return SSNT_ERR_UNSUPPORTED;
   // (a sweep addresses one utterance's workspace rows with 32-bit offsets)
   if ((size_t)(a.Imax + 1) * a.Wcap * sizeof(xf) > 0x7fffffffu) return SSNT_ERR_UNSUPPORTED;
   // the gradient launch reads one utterance's class log-probs through a buffer descriptor of
   // Imax*D*4 bytes with 32-bit lane offsets: past 2 GB it would read zeros
   if ((size_t)a.Imax * a.D * sizeof(float) > 0x7fffffffu) return SSNT_ERR_UNSUPPORTED;
-  if (!a.workspace || a.workspace_bytes < v2_fwd_bwd_workspace_bytes(a.B, a.Imax, a.X - 1, a.test_mode))
-    return SSNT_ERR_WORKSPACE;
+  return SSNT_OK;
+}
+
+int f4_dispatch(const V2FwdBwdArgs& a, size_t lds, size_t glds, hipStream_t st) {
   if (a.D <= 8) return launch_f4<8>(a, lds, glds, st);
   if (a.D <= 16) return launch_f4<16>(a, lds, glds, st);
   if (a.D <= 32) return launch_f4<32>(a, lds, glds, st);
   return launch_f4<64>(a, lds, glds, st);
+}
+}  // namespace
+
+int launch_v2_fwd_bwd(const V2FwdBwdArgs& in, hipStream_t st) {
+  V2FwdBwdArgs a = in;
+  a.fwd_only = false;
+  size_t lds = 0, glds = 0;
+  const int rc = f4_plan(a, true, lds, glds);
+  if (rc != SSNT_OK || a.B == 0) return rc;
+  if (!a.workspace || a.workspace_bytes < v2_fwd_bwd_workspace_bytes(a.B, a.Imax, a.X - 1, a.test_mode))
+    return SSNT_ERR_WORKSPACE;
+  return f4_dispatch(a, lds, glds, st);
+}
+
+int launch_v2_fwd_only(const V2FwdBwdArgs& in, bool launch, hipStream_t st) {
+  V2FwdBwdArgs a = in;
+  a.fwd_only = true;
+  a.grad = nullptr;
+  a.log_alpha = a.log_beta = nullptr;
+  size_t lds = 0, glds = 0;
+  const int rc = f4_plan(a, false, lds, glds);
+  if (rc != SSNT_OK || a.B == 0) return rc;
+  if (!a.workspace || a.workspace_bytes < v2_fwd_only_workspace_bytes(a.B, a.Imax, a.X - 1, a.test_mode))
+    return SSNT_ERR_WORKSPACE;
+  return launch ? f4_dispatch(a, lds, glds, st) : SSNT_OK;
 }
 
 }  // namespace ssnt

@@ -6,7 +6,9 @@ The function names, argument order and meaning mirror the reference's Python op 
 of ``lib/libssnt_tts_c.so`` (include/ssnt_tts_c.h) on torch's current HIP stream; there is no CPU
 fallback. Added beside them: the lattice forward-backward (``ssnt_fwd_bwd``,
 ``SSNTLatticeLoss``), the exact best path over the same lattice (``ssnt_viterbi_align``),
-alignments drawn from its posterior (``ssnt_sample_align``) and a fused multi-step decode (``lattice_beam_search_decode``).
+alignments drawn from its posterior (``ssnt_sample_align``), their counterparts on the v2
+duration-class lattice (``v2_fwd_bwd``, ``v2_viterbi_align``, ``v2_sample_align``) and a fused
+multi-step decode (``lattice_beam_search_decode``).
 
 Errors the reference raises by panicking (v2 "no candidate", upsample duration mismatch,
 out-of-range branch) are raised here as ``SsntError`` when ``check=True`` (the default), which
@@ -30,7 +32,8 @@ __all__ = [
     "SSNTLatticeLoss",
     "ssnt_lattice_loss",
     "lattice_beam_search_decode", "v2_lattice_beam_search_decode",
-    "tone_latent_lattice_beam_search_decode", "v2_fwd_bwd", "v2_viterbi_align", "V2DurationLoss",
+    "tone_latent_lattice_beam_search_decode", "v2_fwd_bwd", "v2_viterbi_align", "v2_sample_align",
+    "V2DurationLoss",
     "v2_duration_loss",
     "SsntError", "FLAG_TERMINAL_EMIT", "FLAG_ZERO_INFINITY",
 ]
@@ -595,6 +598,63 @@ def v2_viterbi_align(logits, duration_table, input_length, output_length, zero_d
                                           _p(ws), wsb, _p(st), _stream(dev))
     _finish("v2_viterbi_align", rc, st, check)
     res = {"log_prob": lp, "status": st}
+    if need_path:
+        res["duration_class"] = cls
+        res["duration"] = dur
+        res["total"] = tot
+    return res
+
+
+def v2_sample_align(logits, duration_table, input_length, output_length, zero_duration_id,
+                    num_samples, *, uniform=None, generator=None, allow_skip=False,
+                    test_mode=False, max_total=None, need_path=True, check=False, out=None):
+    """Duration paths drawn from the posterior of the v2 duration-class lattice.
+
+    Inputs as ``v2_fwd_bwd`` (``max_total`` defaults to max(output_length), read back from the
+    device); ``num_samples`` K in [1, 64] class sequences per utterance. ``uniform`` (B,K,T+1) f32
+    is the randomness: [b,k,t] chooses the class of step t, [b,k,T] the final total (clamped to
+    [0, 1 - 2^-24], NaN counts as 0); without it ``torch.rand((B,K,T+1), generator=generator)`` is
+    drawn on the device. The call is a pure function of its tensors. Returns a dict with
+    ``log_prob`` (B,K) f32, the log-probability of each drawn sequence; ``duration_class`` (B,K,T)
+    i32 (-1 for steps >= I_b), ``duration`` (B,K,T) i32 = duration_table[class] (0 for steps >=
+    I_b) and ``total`` (B,K) i32 as ``v2_viterbi_align``, per sample; ``uniform``, the numbers
+    used; ``status``. An utterance without an admissible path gets -inf, -1, 0 and -1 for every
+    sample. ``need_path=False`` writes ``log_prob`` only. ``out`` may pass preallocated tensors
+    under the same keys."""
+    lib = load(require_gpu=True)
+    lg = _dev(logits, torch.float32, "logits")
+    dev = lg.device
+    B, T, D = lg.shape
+    K = int(num_samples)
+    table = _dev(duration_table, torch.int32, "duration_table").reshape(D)
+    il = _dev(input_length, torch.int32, "input_length").reshape(B)
+    ol = _dev(output_length, torch.int32, "output_length").reshape(B)
+    if max_total is None:
+        max_total = int(ol.max().item()) if B > 0 else 0
+    if uniform is None:
+        un = torch.rand((B, K, T + 1), device=dev, dtype=torch.float32, generator=generator)
+    else:
+        un = _dev(uniform, torch.float32, "uniform")
+        if tuple(un.shape) != (B, K, T + 1):
+            raise ValueError(f"uniform must be (B,K,T+1) = {(B, K, T + 1)}")
+    out = dict(out or {})
+    lp = _buf(out, dev, "log_prob", (B, K), torch.float32)
+    cls = _buf(out, dev, "duration_class", (B, K, T), torch.int32, want=need_path)
+    dur = _buf(out, dev, "duration", (B, K, T), torch.int32, want=need_path)
+    tot = _buf(out, dev, "total", (B, K), torch.int32, want=need_path)
+    wsb = int(lib.ssnt_v2_sample_align_workspace_size(B, T, int(max_total), bool(test_mode), K))
+    ws = _workspace(dev, wsb)
+    st = out.get("status")
+    if st is None:
+        st = _status(dev)
+    else:
+        st.zero_()
+    rc = lib.ssnt_v2_sample_align_device(_p(lg), _p(table), _p(il), _p(ol), _p(un), B, T, D,
+                                         int(max_total), int(zero_duration_id), bool(allow_skip),
+                                         bool(test_mode), K, _p(lp), _p(cls), _p(dur), _p(tot),
+                                         _p(ws), wsb, _p(st), _stream(dev))
+    _finish("v2_sample_align", rc, st, check)
+    res = {"log_prob": lp, "uniform": un, "status": st}
     if need_path:
         res["duration_class"] = cls
         res["duration"] = dur
