@@ -198,6 +198,36 @@ int ssnt_viterbi_align_device(const float *log_trans, const float *log_obs, cons
                               float *log_prob, int *position, int *duration, void *workspace,
                               size_t workspace_bytes, int *status, void *stream);
 
+/* ---- the exact N best alignments on the emit/shift lattice ----
+ * The beam search over this lattice with an unbounded beam, truncated to num_best: every cell of
+ * the recurrence of ssnt_viterbi_align_device keeps the num_best best prefixes instead of one,
+ * ordered by (value descending; on equal values the emit before the shift, then the better-ranked
+ * predecessor). IEEE f32 adds and compares only, in the order DESIGN.md 2.6 states, so the outputs
+ * are bit-identical to a plain f32 restatement, a rank's result does not depend on num_best, and
+ * num_best = 1 is ssnt_viterbi_align_device. log_prob (B, num_best) = the log-probabilities of the
+ * num_best most probable monotone alignments, non-increasing (with the terminal emit under
+ * SSNT_FLAG_TERMINAL_EMIT, the only flag accepted); the alignments are pairwise distinct and each
+ * one's sequential f32 sum is its log_prob. position (B, num_best, T) and duration
+ * (B, num_best, U) as ssnt_viterbi_align_device, per rank (NULL = skip). A rank beyond the number
+ * of alignments with positive probability is absent: log_prob -inf, positions -1, durations 0;
+ * present ranks come first. An infeasible utterance (S_b < P_b, S_b = 0, P_b = 0, rank 0 absent,
+ * or a length beyond the tensor, which also sets SSNT_ERR_BAD_LENGTH in `status`) has every rank
+ * absent. -inf inputs are legal; NaN and +inf inputs give unspecified values, but every access
+ * stays inside its buffers, positions in [-1, U) and durations in [0, T]. The input cells
+ * ssnt_fwd_bwd_device never reads into a result are never read into one here. num_best outside
+ * [1, 8] returns SSNT_ERR_INVALID_ARG. Supported: max_pos <= 1024 for num_best <= 2, <= 512 for
+ * num_best <= 4, <= 256 for num_best <= 8; beyond that SSNT_ERR_UNSUPPORTED. `workspace` holds
+ * ssnt_nbest_align_workspace_size() bytes, 8-byte aligned: 0 (NULL workspace) while the
+ * backpointers of one utterance fit LDS; with position and duration both NULL no backpointers
+ * are kept and no workspace is needed. A refused call writes nothing. Device pointers,
+ * asynchronous on `stream`. New: the reference only searches this lattice with a pruned beam. */
+size_t ssnt_nbest_align_workspace_size(int batch, int max_steps, int max_pos, int num_best);
+int ssnt_nbest_align_device(const float *log_trans, const float *log_obs, const int *step_len,
+                            const int *pos_len, int batch, int max_steps, int max_pos,
+                            int num_best, int flags, float *log_prob, int *position,
+                            int *duration, void *workspace, size_t workspace_bytes, int *status,
+                            void *stream);
+
 /* ---- alignments drawn from the posterior of the emit/shift lattice ----
  * Forward filter, backward sample over the tensors of ssnt_fwd_bwd_device: the forward sweep is
  * the forward-backward's alpha recurrence in split-exponent f32; walking back from (S_b-1, P_b-1),

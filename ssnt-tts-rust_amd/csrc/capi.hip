@@ -809,6 +809,24 @@ int ssnt_viterbi_align_device(const float* log_trans, const float* log_obs, cons
   return launch_viterbi(a, as_stream(stream));
 }
 
+size_t ssnt_nbest_align_workspace_size(int batch, int max_steps, int max_pos, int num_best) {
+  if (batch <= 0 || max_steps <= 0 || max_pos <= 0) return 0;
+  return nbest_align_workspace_bytes(batch, max_steps, max_pos, num_best);
+}
+
+int ssnt_nbest_align_device(const float* log_trans, const float* log_obs, const int* step_len,
+                            const int* pos_len, int batch, int max_steps, int max_pos,
+                            int num_best, int flags, float* log_prob, int* position,
+                            int* duration, void* workspace, size_t workspace_bytes, int* status,
+                            void* stream) {
+  NbestAlignArgs a{};
+  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
+  a.B = batch; a.T = max_steps; a.U = max_pos; a.N = num_best; a.flags = flags;
+  a.log_prob = log_prob; a.position = position; a.duration = duration;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  return launch_nbest_align(a, as_stream(stream));
+}
+
 size_t ssnt_sample_align_workspace_size(int batch, int max_steps, int max_pos, int num_samples) {
   if (batch <= 0 || max_steps <= 0 || max_pos <= 0 || max_pos > 1024 || num_samples < 1 || num_samples > 64)
     return 0;

@@ -100,6 +100,23 @@ struct ViterbiArgs {
 size_t viterbi_workspace_bytes(int B, int T, int U);
 int launch_viterbi(const ViterbiArgs& a, hipStream_t stream);
 
+// ---- the exact N best alignments on the emit/shift lattice (nbest_align.hip) ----
+struct NbestAlignArgs {
+  const float* log_trans;  // (B,T,U,2)
+  const float* log_obs;    // (B,T,U) or null
+  const int* step_len;     // (B)
+  const int* pos_len;      // (B)
+  int B, T, U, N, flags;   // N: alignments per utterance, 1..8
+  float* log_prob;   // (B,N)
+  int* position;     // (B,N,T) or null
+  int* duration;     // (B,N,U) or null
+  void* workspace;   // backpointer tags when they do not fit LDS
+  size_t workspace_bytes;
+  int* status;
+};
+size_t nbest_align_workspace_bytes(int B, int T, int U, int N);
+int launch_nbest_align(const NbestAlignArgs& a, hipStream_t stream);
+
 // ---- alignments drawn from the posterior of the emit/shift lattice (sample_align.hip) ----
 struct SampleAlignArgs {
   const float* log_trans;  // (B,T,U,2)

@@ -6,7 +6,8 @@ The function names, argument order and meaning mirror the reference's Python op 
 of ``lib/libssnt_tts_c.so`` (include/ssnt_tts_c.h) on torch's current HIP stream; there is no CPU
 fallback. Added beside them: the lattice forward-backward (``ssnt_fwd_bwd``,
 ``SSNTLatticeLoss``), the exact best path over the same lattice (``ssnt_viterbi_align``),
-alignments drawn from its posterior (``ssnt_sample_align``), their counterparts on the v2
+the exact N best alignments (``ssnt_nbest_align``), alignments drawn from its posterior
+(``ssnt_sample_align``), the counterparts of the first three on the v2
 duration-class lattice (``v2_fwd_bwd``, ``v2_viterbi_align``, ``v2_sample_align``) and a fused
 multi-step decode (``lattice_beam_search_decode``).
 
@@ -29,7 +30,7 @@ __all__ = [
     "beam_search_decode", "extract_best_beam_branch", "ssnt_tts_v2_beam_search_decode",
     "order_beam_branch", "upsample_source_indexes", "tone_latent_beam_search_decode",
     "levenshtein_edit_distance", "ssnt_fwd_bwd", "ssnt_viterbi_align", "ssnt_sample_align",
-    "SSNTLatticeLoss",
+    "ssnt_nbest_align", "SSNTLatticeLoss",
     "ssnt_lattice_loss",
     "lattice_beam_search_decode", "v2_lattice_beam_search_decode",
     "tone_latent_lattice_beam_search_decode", "v2_fwd_bwd", "v2_viterbi_align", "v2_sample_align",
@@ -422,6 +423,45 @@ def ssnt_viterbi_align(log_trans, step_len, pos_len, log_obs=None, *, terminal_e
                                        _p(pos), _p(dur), _p(ws), wsb, _p(st), _stream(dev))
     _finish("ssnt_viterbi_align", rc, st, check)
     res = {"log_prob": lp, "status": st}
+    if need_path:
+        res["position"] = pos
+        res["duration"] = dur
+    return res
+
+
+def ssnt_nbest_align(log_trans, step_len, pos_len, num_best, log_obs=None, *, terminal_emit=True,
+                     need_path=True, check=False, out=None):
+    """The exact N best alignments over the emit/shift lattice.
+
+    Inputs as ``ssnt_fwd_bwd``; ``num_best`` N in [1, 8] (U <= 1024 / 512 / 256 for N <= 2 / 4 /
+    8). Returns a dict with ``log_prob`` (B,N) f32, the log-probabilities of the N most probable
+    monotone alignments, non-increasing; ``position`` (B,N,T) i32 and ``duration`` (B,N,U) i32 as
+    ``ssnt_viterbi_align``, per rank; ``count`` (B,) i32, the number of present ranks; ``status``.
+    The alignments of an utterance are pairwise distinct; rank 0 is ``ssnt_viterbi_align``'s. A
+    rank beyond the number of alignments with positive probability is absent (-inf, -1 and 0);
+    an infeasible utterance has every rank absent. ``need_path=False`` computes ``log_prob`` and
+    ``count`` only. ``out`` may pass preallocated tensors under the same keys (not ``count``)."""
+    lib = load(require_gpu=True)
+    lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit)
+    dev = lt.device
+    B, T, U, _ = lt.shape
+    N = int(num_best)
+    out = dict(out or {})
+    shape_n = max(N, 0)  # (an N the library refuses: the call below reports it)
+    lp = _buf(out, dev, "log_prob", (B, shape_n), torch.float32)
+    pos = _buf(out, dev, "position", (B, shape_n, T), torch.int32, want=need_path)
+    dur = _buf(out, dev, "duration", (B, shape_n, U), torch.int32, want=need_path)
+    wsb = int(lib.ssnt_nbest_align_workspace_size(B, T, U, N)) if need_path else 0
+    ws = _workspace(dev, wsb)
+    st = out.get("status")
+    if st is None:
+        st = _status(dev)
+    else:
+        st.zero_()
+    rc = lib.ssnt_nbest_align_device(_p(lt), _p(lo), _p(sl), _p(pl), B, T, U, N, flags, _p(lp),
+                                     _p(pos), _p(dur), _p(ws), wsb, _p(st), _stream(dev))
+    _finish("ssnt_nbest_align", rc, st, check)
+    res = {"log_prob": lp, "count": (lp > float("-inf")).sum(dim=1).to(torch.int32), "status": st}
     if need_path:
         res["position"] = pos
         res["duration"] = dur
