@@ -305,6 +305,45 @@ int ssnt_v2_viterbi_align_device(const float *logits, const int *duration_table,
                                  void *workspace, size_t workspace_bytes, int *status,
                                  void *stream);
 
+/* ---- the exact N best duration paths on the v2 duration-class lattice.
+ * ssnt_v2_viterbi_align_device's sweep (same inputs, states, windows and class rule) with a
+ * sorted list of N = num_best entries per cell, 1 <= N <= 8: IEEE f32 adds and ordered compares
+ * under one total order -- value descending, then class, then predecessor rank ascending inside
+ * the lattice; value descending, then final total, then rank ascending in the final selection --
+ * so the outputs are bit-identical to a plain f32 restatement. log_prob (B,N) = the N largest
+ * sequential f32 sums (from 0.0f, in step order) over all admissible class sequences,
+ * non-increasing; duration_class (B,N,T) = the class sequence of each rank (-1 for steps >= I_b);
+ * duration (B,N,T) = duration_table[class] (0 for steps >= I_b); total (B,N) = its final total
+ * (= O_b in band mode). Each of the three may be NULL. The N class sequences of an utterance are
+ * pairwise distinct (two classes of equal duration give distinct sequences with equal duration
+ * rows), each re-sums to its log_prob bit for bit, rank n is the same at every num_best > n, and
+ * num_best = 1 gives ssnt_v2_viterbi_align_device's outputs. A rank beyond the number of
+ * admissible sequences with positive probability is absent: log_prob -inf, classes -1, durations
+ * 0, total -1; present ranks come first. An utterance with no admissible path (I_b = 0, band mode
+ * with O_b > max_total, a length outside the tensor, which also sets SSNT_ERR_BAD_LENGTH in
+ * `status`, or a negative duration, which sets SSNT_ERR_BAD_INDEX) has every rank absent. -inf
+ * logits are legal; NaN and +inf give unspecified values for num_best > 1, and no input takes an
+ * access outside the buffers. Logits rows at steps >= I_b, and column zero_duration_id when
+ * allow_skip is false, are never read into a result. Limits: num_best outside [1, 8] and
+ * max_total outside [0, 1<<24] return SSNT_ERR_INVALID_ARG; duration_class_size > 64, rows
+ * that do not fit LDS at that num_best (2 * NB * (row cells + 130) * 4 bytes beside 8-16 KiB of
+ * class log-probs, NB = num_best rounded up to 1, 2, 4, 8) and backpointers of one utterance
+ * beyond 32-bit offsets SSNT_ERR_UNSUPPORTED. `workspace` holds
+ * ssnt_v2_nbest_align_workspace_size() bytes, 4-byte aligned: 0 (NULL workspace) while the
+ * backpointer entries of one utterance (max_steps * row cells * NB, a byte each, 16 bits at
+ * NB = 8) fit LDS; a missing, short or misaligned one returns SSNT_ERR_WORKSPACE; with
+ * duration_class and duration both NULL no backpointers are kept and no workspace is needed. A
+ * refused call writes nothing. Device pointers, asynchronous on `stream`. New: the reference only
+ * searches this lattice with a pruned beam. */
+size_t ssnt_v2_nbest_align_workspace_size(int batch, int max_steps, int max_total, bool test_mode,
+                                          int num_best);
+int ssnt_v2_nbest_align_device(const float *logits, const int *duration_table,
+                               const int *input_length, const int *output_length, int batch,
+                               int max_steps, int duration_class_size, int max_total,
+                               int zero_duration_id, bool allow_skip, bool test_mode, int num_best,
+                               float *log_prob, int *duration_class, int *duration, int *total,
+                               void *workspace, size_t workspace_bytes, int *status, void *stream);
+
 /* ---- duration paths drawn from the posterior of the v2 duration-class lattice (DESIGN.md 2.5,
  * 5.9). Forward filter, backward sample on F4's lattice (same inputs, states, windows and class
  * rule as ssnt_v2_fwd_bwd_device): the forward rows are F4's alpha, bit for bit; walking back from

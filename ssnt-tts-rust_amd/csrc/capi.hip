@@ -890,6 +890,29 @@ int ssnt_v2_viterbi_align_device(const float* logits, const int* duration_table,
   return launch_v2_viterbi(a, as_stream(stream));
 }
 
+size_t ssnt_v2_nbest_align_workspace_size(int batch, int max_steps, int max_total, bool test_mode,
+                                          int num_best) {
+  if (max_total < 0 || max_total > (1 << 24)) return 0;
+  return v2_nbest_workspace_bytes(batch, max_steps, max_total, test_mode, num_best);
+}
+
+int ssnt_v2_nbest_align_device(const float* logits, const int* duration_table,
+                               const int* input_length, const int* output_length, int batch,
+                               int max_steps, int duration_class_size, int max_total,
+                               int zero_duration_id, bool allow_skip, bool test_mode, int num_best,
+                               float* log_prob, int* duration_class, int* duration, int* total,
+                               void* workspace, size_t workspace_bytes, int* status, void* stream) {
+  if (max_total < 0 || max_total > (1 << 24)) return SSNT_ERR_INVALID_ARG;
+  V2NbestArgs a{};
+  a.logits = logits; a.table = duration_table; a.input_length = input_length;
+  a.output_length = output_length; a.B = batch; a.Imax = max_steps; a.D = duration_class_size;
+  a.X = max_total + 1; a.N = num_best; a.zid = zero_duration_id; a.allow_skip = allow_skip;
+  a.test_mode = test_mode; a.log_prob = log_prob; a.duration_class = duration_class;
+  a.duration = duration; a.total = total; a.workspace = workspace;
+  a.workspace_bytes = workspace_bytes; a.status = status;
+  return launch_v2_nbest_align(a, as_stream(stream));
+}
+
 size_t ssnt_v2_sample_align_workspace_size(int batch, int max_steps, int max_total, bool test_mode,
                                            int num_samples) {
   if (max_total < 0 || max_total > (1 << 24) || num_samples < 1 || num_samples > 64) return 0;

@@ -185,6 +185,27 @@ struct V2ViterbiArgs {
 size_t v2_viterbi_workspace_bytes(int B, int Imax, int max_total, bool test_mode);
 int launch_v2_viterbi(const V2ViterbiArgs& a, hipStream_t stream);
 
+// ---- the exact N best duration paths on the v2 lattice (v2_nbest_align.hip) ----
+struct V2NbestArgs {
+  const float* logits;       // (B, Imax, D) per-step class log-probs
+  const int* table;          // (D) duration_table, >= 0
+  const int* input_length;   // (B) I_b <= Imax
+  const int* output_length;  // (B) O_b
+  int B, Imax, D, X, N;      // X = max_total + 1 totals per row; N: paths per utterance, 1..8
+  int zid;                   // zero_duration_id
+  bool allow_skip, test_mode;
+  float* log_prob;           // (B, N)
+  int* duration_class;       // (B, N, Imax) or null
+  int* duration;             // (B, N, Imax) or null
+  int* total;                // (B, N) or null
+  void* workspace;           // backpointer entries when they do not fit LDS
+  size_t workspace_bytes;
+  int Wcap;                  // set by the launcher
+  int* status;
+};
+size_t v2_nbest_workspace_bytes(int B, int Imax, int max_total, bool test_mode, int N);
+int launch_v2_nbest_align(const V2NbestArgs& a, hipStream_t stream);
+
 // ---- duration paths drawn from the posterior of the v2 lattice (v2_sample_align.hip) ----
 struct V2SampleArgs {
   const float* logits;       // (B, Imax, D) per-step class log-probs

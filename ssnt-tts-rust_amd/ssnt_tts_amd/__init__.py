@@ -8,8 +8,9 @@ fallback. Added beside them: the lattice forward-backward (``ssnt_fwd_bwd``,
 ``SSNTLatticeLoss``), the exact best path over the same lattice (``ssnt_viterbi_align``),
 the exact N best alignments (``ssnt_nbest_align``), alignments drawn from its posterior
 (``ssnt_sample_align``), the counterparts of the first three on the v2
-duration-class lattice (``v2_fwd_bwd``, ``v2_viterbi_align``, ``v2_sample_align``) and a fused
-multi-step decode (``lattice_beam_search_decode``).
+duration-class lattice (``v2_fwd_bwd``, ``v2_viterbi_align``, ``v2_sample_align``), the exact N
+best duration paths on it (``v2_nbest_align``) and a fused multi-step decode
+(``lattice_beam_search_decode``).
 
 Errors the reference raises by panicking (v2 "no candidate", upsample duration mismatch,
 out-of-range branch) are raised here as ``SsntError`` when ``check=True`` (the default), which
@@ -34,7 +35,7 @@ __all__ = [
     "ssnt_lattice_loss",
     "lattice_beam_search_decode", "v2_lattice_beam_search_decode",
     "tone_latent_lattice_beam_search_decode", "v2_fwd_bwd", "v2_viterbi_align", "v2_sample_align",
-    "V2DurationLoss",
+    "v2_nbest_align", "V2DurationLoss",
     "v2_duration_loss",
     "SsntError", "FLAG_TERMINAL_EMIT", "FLAG_ZERO_INFINITY",
 ]
@@ -638,6 +639,57 @@ def v2_viterbi_align(logits, duration_table, input_length, output_length, zero_d
                                           _p(ws), wsb, _p(st), _stream(dev))
     _finish("v2_viterbi_align", rc, st, check)
     res = {"log_prob": lp, "status": st}
+    if need_path:
+        res["duration_class"] = cls
+        res["duration"] = dur
+        res["total"] = tot
+    return res
+
+
+def v2_nbest_align(logits, duration_table, input_length, output_length, zero_duration_id, num_best,
+                   *, allow_skip=False, test_mode=False, max_total=None, need_path=True,
+                   check=False, out=None):
+    """The exact N best duration paths on the v2 duration-class lattice.
+
+    Inputs as ``v2_viterbi_align``; ``num_best`` N in [1, 8]. Returns a dict with ``log_prob``
+    (B,N) f32, the log-probabilities of the N most probable class sequences the v2 move rules
+    admit, non-increasing; ``duration_class`` (B,N,T) i32, ``duration`` (B,N,T) i32 and ``total``
+    (B,N) i32 as ``v2_viterbi_align``, per rank; ``count`` (B,) i32, the number of present ranks;
+    ``status``. The class sequences of an utterance are pairwise distinct; rank 0 is
+    ``v2_viterbi_align``'s. A rank beyond the number of admissible sequences with positive
+    probability is absent (-inf, -1, 0 and -1); an utterance without an admissible path has every
+    rank absent. ``need_path=False`` computes ``log_prob`` and ``count`` only. ``out`` may pass
+    preallocated tensors under the same keys (not ``count``)."""
+    lib = load(require_gpu=True)
+    lg = _dev(logits, torch.float32, "logits")
+    dev = lg.device
+    B, T, D = lg.shape
+    N = int(num_best)
+    table = _dev(duration_table, torch.int32, "duration_table").reshape(D)
+    il = _dev(input_length, torch.int32, "input_length").reshape(B)
+    ol = _dev(output_length, torch.int32, "output_length").reshape(B)
+    if max_total is None:
+        max_total = int(ol.max().item()) if B > 0 else 0
+    out = dict(out or {})
+    shape_n = max(N, 0)  # (an N the library refuses: the call below reports it)
+    lp = _buf(out, dev, "log_prob", (B, shape_n), torch.float32)
+    cls = _buf(out, dev, "duration_class", (B, shape_n, T), torch.int32, want=need_path)
+    dur = _buf(out, dev, "duration", (B, shape_n, T), torch.int32, want=need_path)
+    tot = _buf(out, dev, "total", (B, shape_n), torch.int32, want=need_path)
+    wsb = int(lib.ssnt_v2_nbest_align_workspace_size(B, T, int(max_total), bool(test_mode), N)) \
+        if need_path else 0
+    ws = _workspace(dev, wsb)
+    st = out.get("status")
+    if st is None:
+        st = _status(dev)
+    else:
+        st.zero_()
+    rc = lib.ssnt_v2_nbest_align_device(_p(lg), _p(table), _p(il), _p(ol), B, T, D,
+                                        int(max_total), int(zero_duration_id), bool(allow_skip),
+                                        bool(test_mode), N, _p(lp), _p(cls), _p(dur), _p(tot),
+                                        _p(ws), wsb, _p(st), _stream(dev))
+    _finish("v2_nbest_align", rc, st, check)
+    res = {"log_prob": lp, "count": (lp > float("-inf")).sum(dim=1).to(torch.int32), "status": st}
     if need_path:
         res["duration_class"] = cls
         res["duration"] = dur

@@ -63,6 +63,9 @@ SIGNATURES = {
     "ssnt_v2_viterbi_align_workspace_size": (c_size_t, [c_int, c_int, c_int, c_bool]),
     "ssnt_v2_viterbi_align_device": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_bool,
                                              c_bool, P, P, P, P, P, c_size_t, P, P]),
+    "ssnt_v2_nbest_align_workspace_size": (c_size_t, [c_int, c_int, c_int, c_bool, c_int]),
+    "ssnt_v2_nbest_align_device": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_bool,
+                                           c_bool, c_int, P, P, P, P, P, c_size_t, P, P]),
     "ssnt_v2_sample_align_workspace_size": (c_size_t, [c_int, c_int, c_int, c_bool, c_int]),
     "ssnt_v2_sample_align_device": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_bool,
                                             c_bool, c_int, P, P, P, P, P, c_size_t, P, P]),
