@@ -257,6 +257,40 @@ int ssnt_sample_align_device(const float *log_trans, const float *log_obs, const
                              int *position, int *duration, void *workspace,
                              size_t workspace_bytes, int *status, void *stream);
 
+/* ---- expected path cost and its gradients on the emit/shift lattice ----
+ * The expectation semiring over the tensors of ssnt_fwd_bwd_device: cost (B,T,U,2) f32 is added
+ * to a path's cost when it takes the edge [b,s,p,k] (k = 0 emit, 1 shift; the terminal emit's cost
+ * counts iff SSNT_FLAG_TERMINAL_EMIT, the only flag accepted), and risk (B) = the expectation of
+ * that sum under p(path | log_trans, log_obs). loss (B) = -ln Z as ssnt_fwd_bwd_device, with
+ * Z = alpha[S-1][P-1] * beta[S-1][P-1]. With q the posterior probability of an edge, abar the mean
+ * cost accumulated before a cell and bbar the mean cost from it on (both given that the path
+ * passes the cell): grad_cost (B,T,U,2) = d risk / d cost = q; grad_trans (B,T,U,2) =
+ * d risk / d log_trans = q * (abar[src] + cost + bbar[dst] - risk), exactly 0 for the terminal
+ * emit; grad_obs (B,T,U) = d risk / d log_obs = (alpha*beta/Z) * (abar + bbar - risk). alpha and
+ * beta are the forward-backward's recurrences in split-exponent f32; a mean is the plain f32
+ * convex combination (t1*(m1 + c1) + t2*(m2 + c2)) / (t1 + t2) of the two terms entering the cell
+ * at their common exponent, in both directions. loss and each gradient may be NULL (skip);
+ * grad_obs requires log_obs. Every element of every requested output is written: 0 outside
+ * (S_b, P_b), for the masked shift out of P_b-1 and in row S_b-1, except grad_cost = 1 at the
+ * terminal emit under the flag. An infeasible utterance (S_b < P_b, S_b = 0, P_b = 0, Z = 0, or a
+ * length beyond the tensor, which also sets SSNT_ERR_BAD_LENGTH in `status`) gets risk 0, loss
+ * +inf and gradients 0. -inf in log_trans / log_obs is legal; cost must be finite on the edges
+ * inside the lattice (elsewhere values are unspecified, every access stays in bounds); the
+ * log_trans, log_obs and cost cells ssnt_fwd_bwd_device never reads into a result are never read
+ * into one here. max_pos > 1024 returns SSNT_ERR_UNSUPPORTED, as do log_trans, cost, grad_trans
+ * or grad_cost not 8-byte aligned. `workspace` holds ssnt_expected_cost_workspace_size() bytes,
+ * 8-byte aligned (both sweeps' rows, 12 B per cell and direction); with all three gradients NULL
+ * only the forward sweep runs and the workspace may be NULL; missing or short otherwise:
+ * SSNT_ERR_WORKSPACE. risk and loss have the same bits with and without gradients. A refused
+ * call writes nothing. Device pointers, asynchronous on `stream`. New: the reference has no
+ * expectation over alignments. */
+size_t ssnt_expected_cost_workspace_size(int batch, int max_steps, int max_pos);
+int ssnt_expected_cost_device(const float *log_trans, const float *log_obs, const float *cost,
+                              const int *step_len, const int *pos_len, int batch, int max_steps,
+                              int max_pos, int flags, float *risk, float *loss,
+                              float *grad_trans, float *grad_cost, float *grad_obs,
+                              void *workspace, size_t workspace_bytes, int *status, void *stream);
+
 /* ---- F4: v2 duration-class (semi-Markov) forward-backward (DESIGN.md
  * "Duration lattice"). New: the reference only decodes this lattice; the move rules are the v2
  * decode's (src/v2.rs:94-166 -- band, overrun, exact final total, zero-duration class; test_mode

@@ -36,6 +36,11 @@ int ssnt_fwd_bwd_wide_lag(int sleeps);
  * the forward sweep, bit 1 the walk; 3 default: timing one launch over a workspace an earlier full
  * call left) */
 int ssnt_v2_sample_align_form(int cone, int launches);
+/* expected path cost: the transition rows of one chunk of the sweep for a shape (host query; 0 for
+ * a max_pos it does not take), and the launches that run (bit 0 the sweep, bit 1 the gradient
+ * launch; 3 default: timing one launch over a workspace an earlier full call left) */
+int ssnt_expected_cost_chunk_rows(int max_pos, int has_obs);
+int ssnt_expected_cost_launches(int mask);
 /* per-step reference symbols: host staging 0 copies / 1 zero-copy; completion 0 stream
  * synchronise / 1 hipStreamWriteValue32 word / 2 flag kernel; both return the previous mode */
 int ssnt_set_host_staging(int mode);

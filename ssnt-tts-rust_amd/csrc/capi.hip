@@ -702,6 +702,11 @@ int ssnt_fwd_bwd_wide_split(int mode) { return set_fwd_bwd_wide_split(mode); }
 // receiver proxy runs a whole ring ahead of it (tests/test_gpu_fwd_bwd.py hand-off race test)
 int ssnt_fwd_bwd_wide_lag(int sleeps) { return set_fwd_bwd_wide_lag(sleeps); }
 int ssnt_v2_sample_align_form(int cone, int launches) { return set_v2_sample_form(cone, launches); }
+int ssnt_expected_cost_chunk_rows(int max_pos, int has_obs) {
+  if (max_pos < 1 || max_pos > 1024) return 0;
+  return expected_cost_chunk_rows(max_pos, has_obs != 0);
+}
+int ssnt_expected_cost_launches(int mask) { return set_expected_cost_launches(mask); }
 
 // Per-step symbol latency breakdown (tools/bench_step_symbols.py).
 // enable = 1 resets and starts the calling thread's phase clock; 0 stops it and writes the mean
@@ -844,6 +849,25 @@ int ssnt_sample_align_device(const float* log_trans, const float* log_obs, const
   a.flags = flags; a.log_prob = log_prob; a.position = position; a.duration = duration;
   a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
   return launch_sample_align(a, as_stream(stream));
+}
+
+size_t ssnt_expected_cost_workspace_size(int batch, int max_steps, int max_pos) {
+  if (batch <= 0 || max_steps <= 0 || max_pos <= 0 || max_pos > 1024) return 0;
+  return expected_cost_workspace_bytes(batch, max_steps, max_pos);
+}
+
+int ssnt_expected_cost_device(const float* log_trans, const float* log_obs, const float* cost,
+                              const int* step_len, const int* pos_len, int batch, int max_steps,
+                              int max_pos, int flags, float* risk, float* loss, float* grad_trans,
+                              float* grad_cost, float* grad_obs, void* workspace,
+                              size_t workspace_bytes, int* status, void* stream) {
+  ExpectedCostArgs a{};
+  a.log_trans = log_trans; a.log_obs = log_obs; a.cost = cost; a.step_len = step_len;
+  a.pos_len = pos_len; a.B = batch; a.T = max_steps; a.U = max_pos; a.flags = flags;
+  a.risk = risk; a.loss = loss; a.grad_trans = grad_trans; a.grad_cost = grad_cost;
+  a.grad_obs = grad_obs; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  a.status = status;
+  return launch_expected_cost(a, as_stream(stream));
 }
 
 size_t ssnt_v2_fwd_bwd_workspace_size(int batch, int max_steps, int max_total, bool test_mode) {

@@ -135,6 +135,32 @@ struct SampleAlignArgs {
 size_t sample_align_workspace_bytes(int B, int T, int U, int NS);
 int launch_sample_align(const SampleAlignArgs& a, hipStream_t stream);
 
+// ---- expected path cost and its gradients on the emit/shift lattice (expected_cost.hip) ----
+struct ExpectedCostArgs {
+  const float* log_trans;  // (B,T,U,2)
+  const float* log_obs;    // (B,T,U) or null
+  const float* cost;       // (B,T,U,2): added to a path's cost when it takes the edge
+  const int* step_len;     // (B)
+  const int* pos_len;      // (B)
+  int B, T, U, flags;
+  float* risk;        // (B)
+  float* loss;        // (B) or null
+  float* grad_trans;  // (B,T,U,2) or null
+  float* grad_cost;   // (B,T,U,2) or null
+  float* grad_obs;    // (B,T,U) or null (requires log_obs)
+  void* workspace;    // Z and risk per utterance, then both chains' rows; gradients only
+  size_t workspace_bytes;
+  int* status;
+};
+size_t expected_cost_workspace_bytes(int B, int T, int U);
+int launch_expected_cost(const ExpectedCostArgs& a, hipStream_t stream);
+#ifdef SSNT_AB
+// the transition rows of one chunk of the sweep for this shape, and which launches run (bit 0 the
+// sweep, bit 1 the gradient launch; 3 default)
+int expected_cost_chunk_rows(int U, bool obs);
+int set_expected_cost_launches(int mask);
+#endif
+
 // ---- F4: v2 duration-class forward-backward (v2_fwd_bwd.hip) ----
 struct V2FwdBwdArgs {
   const float* logits;       // (B, Imax, D) per-step class log-probs

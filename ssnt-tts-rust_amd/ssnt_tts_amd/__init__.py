@@ -7,7 +7,8 @@ of ``lib/libssnt_tts_c.so`` (include/ssnt_tts_c.h) on torch's current HIP stream
 fallback. Added beside them: the lattice forward-backward (``ssnt_fwd_bwd``,
 ``SSNTLatticeLoss``), the exact best path over the same lattice (``ssnt_viterbi_align``),
 the exact N best alignments (``ssnt_nbest_align``), alignments drawn from its posterior
-(``ssnt_sample_align``), the counterparts of the first three on the v2
+(``ssnt_sample_align``), the posterior expectation of an additive path cost with its gradients
+(``ssnt_expected_cost``, ``SSNTExpectedCost``, ``ssnt_alignment_entropy``), the counterparts of the first three on the v2
 duration-class lattice (``v2_fwd_bwd``, ``v2_viterbi_align``, ``v2_sample_align``), the exact N
 best duration paths on it (``v2_nbest_align``) and a fused multi-step decode
 (``lattice_beam_search_decode``).
@@ -32,6 +33,7 @@ __all__ = [
     "order_beam_branch", "upsample_source_indexes", "tone_latent_beam_search_decode",
     "levenshtein_edit_distance", "ssnt_fwd_bwd", "ssnt_viterbi_align", "ssnt_sample_align",
     "ssnt_nbest_align", "SSNTLatticeLoss",
+    "ssnt_expected_cost", "SSNTExpectedCost", "ssnt_expected_cost_loss", "ssnt_alignment_entropy",
     "ssnt_lattice_loss",
     "lattice_beam_search_decode", "v2_lattice_beam_search_decode",
     "tone_latent_lattice_beam_search_decode", "v2_fwd_bwd", "v2_viterbi_align", "v2_sample_align",
@@ -544,6 +546,113 @@ def ssnt_lattice_loss(log_trans, step_len, pos_len, log_obs=None, terminal_emit=
                       zero_infinity=False, check=True):
     return SSNTLatticeLoss.apply(log_trans, step_len, pos_len, log_obs, terminal_emit,
                                  zero_infinity, check)
+
+
+def ssnt_expected_cost(log_trans, cost, step_len, pos_len, log_obs=None, *, terminal_emit=True,
+                       need_grad=True, check=False, out=None):
+    """The posterior expectation of an additive path cost on the emit/shift lattice, and its
+    gradients (the expectation semiring).
+
+    Inputs as ``ssnt_fwd_bwd``; ``cost`` (B,T,U,2) f32 is added to a path's cost when it takes the
+    edge [b,s,p,k] (the terminal emit's cost counts iff ``terminal_emit``). Returns a dict with
+    ``risk`` (B,) = E[cost of the path], ``loss`` (B,) = -ln Z, ``status`` and, with ``need_grad``,
+    ``grad_trans`` (B,T,U,2) = d risk / d log_trans, ``grad_cost`` (B,T,U,2) = d risk / d cost (the
+    edge posterior) and ``grad_obs`` (B,T,U) = d risk / d log_obs (if ``log_obs`` is given). An
+    infeasible utterance gets risk 0, loss +inf and gradients 0. ``need_grad=False`` runs the
+    forward sweep alone and returns the same bits of ``risk`` and ``loss``. ``out`` may pass
+    preallocated tensors under the same keys."""
+    lib = load(require_gpu=True)
+    lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit)
+    dev = lt.device
+    B, T, U, _ = lt.shape
+    cs = _dev(cost, torch.float32, "cost")
+    if tuple(cs.shape) != (B, T, U, 2):
+        raise ValueError(f"cost must be (B,T,U,2) = {(B, T, U, 2)}")
+    out = dict(out or {})
+    f32 = {"dtype": torch.float32, "name": "float32"}
+    risk = _buf(out, dev, "risk", (B,), **f32)
+    loss = _buf(out, dev, "loss", (B,), **f32)
+    gt = _buf(out, dev, "grad_trans", (B, T, U, 2), want=need_grad, **f32)
+    gc = _buf(out, dev, "grad_cost", (B, T, U, 2), want=need_grad, **f32)
+    go = _buf(out, dev, "grad_obs", (B, T, U), want=need_grad and lo is not None, **f32)
+    wsb = int(lib.ssnt_expected_cost_workspace_size(B, T, U)) if need_grad else 0
+    ws = _workspace(dev, wsb)
+    st = out.get("status")
+    if st is None:
+        st = _status(dev)
+    else:
+        st.zero_()
+    rc = lib.ssnt_expected_cost_device(_p(lt), _p(lo), _p(cs), _p(sl), _p(pl), B, T, U, flags,
+                                       _p(risk), _p(loss), _p(gt), _p(gc), _p(go), _p(ws), wsb,
+                                       _p(st), _stream(dev))
+    _finish("ssnt_expected_cost", rc, st, check)
+    res = {"risk": risk, "loss": loss, "status": st}
+    if need_grad:
+        res["grad_trans"] = gt
+        res["grad_cost"] = gc
+        if go is not None:
+            res["grad_obs"] = go
+    return res
+
+
+class SSNTExpectedCost(torch.autograd.Function):
+    """Autograd wrapper: per-utterance risk (B,), differentiable with respect to log_trans, cost
+    and log_obs; the gradients come from the same call. The status word is checked in backward,
+    as SSNTLatticeLoss does (check=False skips it)."""
+
+    @staticmethod
+    def forward(ctx, log_trans, cost, step_len, pos_len, log_obs=None, terminal_emit=True, check=True):
+        need = (log_trans.requires_grad or cost.requires_grad
+                or (log_obs is not None and log_obs.requires_grad))
+        r = ssnt_expected_cost(log_trans.detach(), cost.detach(), step_len, pos_len,
+                               None if log_obs is None else log_obs.detach(),
+                               terminal_emit=terminal_emit, need_grad=need)
+        ctx.save_for_backward(r.get("grad_trans"), r.get("grad_cost"), r.get("grad_obs"), r["status"])
+        ctx.check = check
+        return r["risk"]
+
+    @staticmethod
+    def backward(ctx, grad_risk):
+        gt, gc, go, st = ctx.saved_tensors
+        if ctx.check:
+            _finish("ssnt_expected_cost_loss", 0, st, True)
+        gr = grad_risk.to(torch.float32)
+        need_t, need_c, _, _, need_o = ctx.needs_input_grad[:5]
+        dt = gt * gr[:, None, None, None] if need_t and gt is not None else None
+        dc = gc * gr[:, None, None, None] if need_c and gc is not None else None
+        do = go * gr[:, None, None] if need_o and go is not None else None
+        return dt, dc, None, None, do, None, None
+
+
+def ssnt_expected_cost_loss(log_trans, cost, step_len, pos_len, log_obs=None, terminal_emit=True,
+                            check=True):
+    """risk (B,) of ``ssnt_expected_cost``, differentiable (minimum-risk training, expected
+    durations and positions)."""
+    return SSNTExpectedCost.apply(log_trans, cost, step_len, pos_len, log_obs, terminal_emit, check)
+
+
+def ssnt_alignment_entropy(log_trans, step_len, pos_len, log_obs=None, terminal_emit=True):
+    """The entropy H (B,) of the alignment posterior, differentiable: H = ln Z - E[ln w(path)],
+    with ln Z = -loss of ``ssnt_lattice_loss`` and E[ln w] = risk of ``ssnt_expected_cost_loss``
+    for cost = log_trans, plus the log_obs of the entered cell on both edges that enter it (the
+    terminal emit enters none). log_obs[b,0,0] belongs to every path and to no edge; it is in
+    ln Z, so it is subtracted once."""
+    cost = log_trans.to(torch.float32)
+    first = None
+    if log_obs is not None:
+        B, T, U, _ = log_trans.shape
+        lo = log_obs.to(torch.float32).reshape(B, T, U)
+        first = lo[:, 0, 0]
+        pad_s = torch.zeros_like(lo[:, :1])
+        same = torch.cat([lo[:, 1:], pad_s], dim=1)                           # obs[s+1, p]
+        nxt = torch.cat([same[:, :, 1:], torch.zeros_like(same[:, :, :1])], dim=2)  # obs[s+1, p+1]
+        sl = step_len.to(device=lo.device, dtype=torch.int64).reshape(B)
+        inner = torch.arange(T, device=lo.device)[None, :, None, None] < (sl[:, None, None, None] - 1)
+        cost = cost + torch.where(inner, torch.stack([same, nxt], dim=-1), torch.zeros((), device=lo.device))
+    loss = ssnt_lattice_loss(log_trans, step_len, pos_len, log_obs, terminal_emit)
+    risk = ssnt_expected_cost_loss(log_trans, cost, step_len, pos_len, log_obs, terminal_emit)
+    h = -loss - risk
+    return h if first is None else h - first
 
 
 # ----------------------------------------------------------------------------------------------

@@ -57,6 +57,9 @@ SIGNATURES = {
     "ssnt_sample_align_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int]),
     "ssnt_sample_align_device": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P,
                                          P, c_size_t, P, P]),
+    "ssnt_expected_cost_workspace_size": (c_size_t, [c_int, c_int, c_int]),
+    "ssnt_expected_cost_device": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P,
+                                          P, c_size_t, P, P]),
     "ssnt_v2_fwd_bwd_workspace_size": (c_size_t, [c_int, c_int, c_int, c_bool]),
     "ssnt_v2_fwd_bwd_device": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_bool,
                                        c_bool, c_int, P, P, P, P, P, c_size_t, P, P]),
@@ -97,6 +100,8 @@ AB_SIGNATURES = {
     "ssnt_fwd_bwd_wide_split": (c_int, [c_int]),
     "ssnt_fwd_bwd_wide_lag": (c_int, [c_int]),
     "ssnt_v2_sample_align_form": (c_int, [c_int, c_int]),
+    "ssnt_expected_cost_chunk_rows": (c_int, [c_int, c_int]),
+    "ssnt_expected_cost_launches": (c_int, [c_int]),
     "ssnt_set_host_staging": (c_int, [c_int]),
     "ssnt_set_host_sync": (c_int, [c_int]),
     "ssnt_diag_step_clock": (c_int, [c_int, c_void_p]),
@@ -170,6 +175,7 @@ class use_ab:
             ab.ssnt_fwd_bwd_wide_split(-1)
             ab.ssnt_fwd_bwd_wide_lag(0)
             ab.ssnt_v2_sample_align_form(0, 3)
+            ab.ssnt_expected_cost_launches(3)
             ab.ssnt_set_host_staging(1)
             ab.ssnt_set_host_sync(2)
             _active = None
