@@ -312,6 +312,46 @@ int ssnt_v2_fwd_bwd_device(const float *logits, const int *duration_table, const
                            float *log_alpha, float *log_beta, void *workspace,
                            size_t workspace_bytes, int *status, void *stream);
 
+/* ---- expected path cost and its gradients on the v2 duration-class lattice ----
+ * The expectation semiring over F4's lattice: inputs, states, windows, class rule, duration_table,
+ * zero_duration_id, allow_skip, test_mode and max_total are those of ssnt_v2_fwd_bwd_device. cost
+ * (B,T,D) f32 is added to a path's cost when step t takes class i, and risk (B) = the expectation
+ * of that sum under the posterior over admissible class sequences; loss (B) = -ln Z, the bits of
+ * ssnt_v2_fwd_bwd_device. With q(t,x,i) = alpha[t][x] w[t][i] beta[t+1][x+d_i] / Z, abar the mean
+ * cost accumulated before a state and bbar the mean cost from it on (both given that the path
+ * passes the state): grad_cost (B,T,D) = d risk / d cost = sum_x q, the class posterior (the bits
+ * of minus ssnt_v2_fwd_bwd_device's grad); grad_logits (B,T,D) = d risk / d logits =
+ * sum_x q * (abar[t][x] + cost[t,i] + bbar[t+1][x+d_i] - risk). alpha and beta are F4's, bit for
+ * bit; a mean is the plain f32 convex combination of a cell's D terms at their common exponent
+ * (pairwise tree, one division per cell), in both directions. loss and each gradient may be NULL
+ * (skip). Every element of every requested output is written: gradient rows at steps >= I_b are 0,
+ * as is column zero_duration_id when allow_skip is false. An utterance with no admissible path
+ * (I_b = 0, band mode with O_b > max_total, Z = 0, a length outside the tensor, which also sets
+ * SSNT_ERR_BAD_LENGTH in `status`, or a negative duration, which sets SSNT_ERR_BAD_INDEX) gets
+ * risk 0, loss +inf and gradients 0. -inf logits are legal; a move of weight zero contributes an
+ * exact 0 whatever its cost holds (-inf, NaN and +inf included), so cost = logits gives the
+ * entropy; where the weight is non-zero cost must be finite. logits and cost rows at steps >= I_b,
+ * and column zero_duration_id of both when allow_skip is false, are never read into a result, nor
+ * are the previous contents of the outputs and the workspace. duration_class_size > 64 returns
+ * SSNT_ERR_UNSUPPORTED, as does a row that does not fit LDS beside its means: 24 bytes per row
+ * cell and 12 per staged class, so at 16 classes test mode takes max_total up to about 5,600 (F4,
+ * 16 and 8 bytes: about 9,000) and band mode max_total up to about 37,000. max_total outside [0, 1<<24] returns
+ * SSNT_ERR_INVALID_ARG. With a gradient requested, `workspace` holds
+ * ssnt_v2_expected_cost_workspace_size(.., need_grad = true) bytes, 8-byte aligned (F4's rows plus
+ * the two mean rows); missing, short or misaligned: SSNT_ERR_WORKSPACE. With both gradients NULL
+ * only the forward sweep runs, no row is kept, the size is 0 and the workspace may be NULL. risk
+ * and loss have the same bits with and without gradients, and a result does not depend on the
+ * batch around the utterance. A refused call writes nothing. Device pointers, asynchronous on
+ * `stream`. New: the reference has no expectation over duration paths. */
+size_t ssnt_v2_expected_cost_workspace_size(int batch, int max_steps, int max_total,
+                                            bool test_mode, bool need_grad);
+int ssnt_v2_expected_cost_device(const float *logits, const float *cost, const int *duration_table,
+                                 const int *input_length, const int *output_length, int batch,
+                                 int max_steps, int duration_class_size, int max_total,
+                                 int zero_duration_id, bool allow_skip, bool test_mode,
+                                 float *risk, float *loss, float *grad_logits, float *grad_cost,
+                                 void *workspace, size_t workspace_bytes, int *status, void *stream);
+
 /* ---- exact best duration path (Viterbi) on the v2 duration-class lattice.
  * The max-plus recurrence over F4's lattice (same inputs, states, windows and class rule as
  * ssnt_v2_fwd_bwd_device): IEEE f32 adds and strict compares, classes in increasing order (a tie

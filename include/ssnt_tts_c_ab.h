@@ -41,6 +41,11 @@ int ssnt_v2_sample_align_form(int cone, int launches);
  * launch; 3 default: timing one launch over a workspace an earlier full call left) */
 int ssnt_expected_cost_chunk_rows(int max_pos, int has_obs);
 int ssnt_expected_cost_launches(int mask);
+/* expected duration-path cost: the sweep steps of one staged chunk for a class count (host query;
+ * 0 beyond 64 classes), and the launches of the full call that run (bit 0 the sweeps, bit 1 the
+ * gradient launch; 3 default: timing one launch over a workspace an earlier full call left) */
+int ssnt_v2_expected_cost_chunk_steps(int duration_class_size);
+int ssnt_v2_expected_cost_launches(int mask);
 /* per-step reference symbols: host staging 0 copies / 1 zero-copy; completion 0 stream
  * synchronise / 1 hipStreamWriteValue32 word / 2 flag kernel; both return the previous mode */
 int ssnt_set_host_staging(int mode);

@@ -707,6 +707,11 @@ int ssnt_expected_cost_chunk_rows(int max_pos, int has_obs) {
   return expected_cost_chunk_rows(max_pos, has_obs != 0);
 }
 int ssnt_expected_cost_launches(int mask) { return set_expected_cost_launches(mask); }
+int ssnt_v2_expected_cost_chunk_steps(int duration_class_size) {
+  if (duration_class_size < 1 || duration_class_size > 64) return 0;
+  return v2_expected_cost_chunk_steps(duration_class_size);
+}
+int ssnt_v2_expected_cost_launches(int mask) { return set_v2_expected_cost_launches(mask); }
 
 // Per-step symbol latency breakdown (tools/bench_step_symbols.py).
 // enable = 1 resets and starts the calling thread's phase clock; 0 stops it and writes the mean
@@ -889,6 +894,29 @@ int ssnt_v2_fwd_bwd_device(const float* logits, const int* duration_table, const
   a.log_alpha = log_alpha; a.log_beta = log_beta; a.workspace = workspace;
   a.workspace_bytes = workspace_bytes; a.status = status;
   return launch_v2_fwd_bwd(a, as_stream(stream));
+}
+
+size_t ssnt_v2_expected_cost_workspace_size(int batch, int max_steps, int max_total,
+                                            bool test_mode, bool need_grad) {
+  if (max_total < 0 || max_total > (1 << 24)) return 0;
+  return v2_expected_cost_workspace_bytes(batch, max_steps, max_total, test_mode, need_grad);
+}
+
+int ssnt_v2_expected_cost_device(const float* logits, const float* cost, const int* duration_table,
+                                 const int* input_length, const int* output_length, int batch,
+                                 int max_steps, int duration_class_size, int max_total,
+                                 int zero_duration_id, bool allow_skip, bool test_mode,
+                                 float* risk, float* loss, float* grad_logits, float* grad_cost,
+                                 void* workspace, size_t workspace_bytes, int* status, void* stream) {
+  if (max_total < 0 || max_total > (1 << 24)) return SSNT_ERR_INVALID_ARG;
+  V2ExpectedCostArgs a{};
+  a.logits = logits; a.cost = cost; a.table = duration_table; a.input_length = input_length;
+  a.output_length = output_length; a.B = batch; a.Imax = max_steps; a.D = duration_class_size;
+  a.X = max_total + 1; a.zid = zero_duration_id; a.allow_skip = allow_skip;
+  a.test_mode = test_mode; a.risk = risk; a.loss = loss; a.grad_logits = grad_logits;
+  a.grad_cost = grad_cost; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  a.status = status;
+  return launch_v2_expected_cost(a, as_stream(stream));
 }
 
 size_t ssnt_v2_viterbi_align_workspace_size(int batch, int max_steps, int max_total, bool test_mode) {

@@ -190,6 +190,33 @@ int launch_v2_fwd_bwd(const V2FwdBwdArgs& a, hipStream_t stream);
 size_t v2_fwd_only_workspace_bytes(int B, int Imax, int max_total, bool test_mode);
 int launch_v2_fwd_only(const V2FwdBwdArgs& a, bool launch, hipStream_t stream);
 
+// ---- expected path cost and its gradients on the v2 lattice (v2_expected_cost.hip) ----
+struct V2ExpectedCostArgs {
+  const float* logits;       // (B, Imax, D) per-step class log-probs
+  const float* cost;         // (B, Imax, D) added to a path's cost when step t takes class i
+  const int* table;          // (D) duration_table, >= 0
+  const int* input_length;   // (B) I_b <= Imax
+  const int* output_length;  // (B) O_b
+  int B, Imax, D, X;         // X = max_total + 1 totals per row
+  int zid;                   // zero_duration_id
+  bool allow_skip, test_mode;
+  float* risk;               // (B)
+  float* loss;               // (B) or null
+  float* grad_logits;        // (B, Imax, D) or null
+  float* grad_cost;          // (B, Imax, D) or null
+  void* workspace;           // F4's rows and Z, the mean rows, risk; gradients only
+  size_t workspace_bytes;
+  int* status;
+};
+size_t v2_expected_cost_workspace_bytes(int B, int Imax, int max_total, bool test_mode, bool need_grad);
+int launch_v2_expected_cost(const V2ExpectedCostArgs& a, hipStream_t stream);
+#ifdef SSNT_AB
+// the sweep steps of one staged chunk for D classes (the instance a call launches), and which
+// launches of the full call run (bit 0 the sweeps, bit 1 the gradient launch; 3 default)
+int v2_expected_cost_chunk_steps(int D);
+int set_v2_expected_cost_launches(int mask);
+#endif
+
 // ---- exact best duration path on the v2 lattice (v2_viterbi.hip) ----
 struct V2ViterbiArgs {
   const float* logits;       // (B, Imax, D) per-step class log-probs

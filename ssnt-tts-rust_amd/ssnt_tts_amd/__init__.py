@@ -10,7 +10,8 @@ the exact N best alignments (``ssnt_nbest_align``), alignments drawn from its po
 (``ssnt_sample_align``), the posterior expectation of an additive path cost with its gradients
 (``ssnt_expected_cost``, ``SSNTExpectedCost``, ``ssnt_alignment_entropy``), the counterparts of the first three on the v2
 duration-class lattice (``v2_fwd_bwd``, ``v2_viterbi_align``, ``v2_sample_align``), the exact N
-best duration paths on it (``v2_nbest_align``) and a fused multi-step decode
+best duration paths on it (``v2_nbest_align``), the expected cost of a duration path on it
+(``v2_expected_cost``, ``V2ExpectedCost``, ``v2_duration_entropy``) and a fused multi-step decode
 (``lattice_beam_search_decode``).
 
 Errors the reference raises by panicking (v2 "no candidate", upsample duration mismatch,
@@ -39,6 +40,7 @@ __all__ = [
     "tone_latent_lattice_beam_search_decode", "v2_fwd_bwd", "v2_viterbi_align", "v2_sample_align",
     "v2_nbest_align", "V2DurationLoss",
     "v2_duration_loss",
+    "v2_expected_cost", "V2ExpectedCost", "v2_expected_cost_loss", "v2_duration_entropy",
     "SsntError", "FLAG_TERMINAL_EMIT", "FLAG_ZERO_INFINITY",
 ]
 
@@ -892,6 +894,111 @@ def v2_duration_loss(logits, duration_table, input_length, output_length, zero_d
     return V2DurationLoss.apply(logits, duration_table, input_length, output_length,
                                 zero_duration_id, allow_skip, test_mode, max_total, zero_infinity,
                                 check)
+
+
+def v2_expected_cost(logits, cost, duration_table, input_length, output_length, zero_duration_id,
+                     *, allow_skip=False, test_mode=False, max_total=None, need_grad=True,
+                     check=False, out=None):
+    """The posterior expectation of an additive per-step, per-class cost on the v2 duration-class
+    lattice, and its gradients (the expectation semiring).
+
+    Inputs as ``v2_fwd_bwd`` (``max_total`` defaults to max(output_length), read back from the
+    device); ``cost`` (B,T,D) f32 is added to a path's cost when step t takes class i. Returns a
+    dict with ``risk`` (B,) = E[cost of the path], ``loss`` (B,) = -ln Z (the bits of
+    ``v2_fwd_bwd``), ``status`` and, with ``need_grad``, ``grad_logits`` (B,T,D) = d risk / d logits
+    and ``grad_cost`` (B,T,D) = d risk / d cost (the class posterior). An utterance without an
+    admissible path gets risk 0, loss +inf and gradients 0. A class of weight zero contributes an
+    exact 0 whatever its cost holds. ``need_grad=False`` runs the forward sweep alone and returns
+    the same bits of ``risk`` and ``loss``. ``out`` may pass preallocated tensors under the same
+    keys."""
+    lib = load(require_gpu=True)
+    lg = _dev(logits, torch.float32, "logits")
+    dev = lg.device
+    B, T, D = lg.shape
+    cs = _dev(cost, torch.float32, "cost")
+    if tuple(cs.shape) != (B, T, D):
+        raise ValueError(f"cost must be (B,T,D) = {(B, T, D)}")
+    table = _dev(duration_table, torch.int32, "duration_table").reshape(D)
+    il = _dev(input_length, torch.int32, "input_length").reshape(B)
+    ol = _dev(output_length, torch.int32, "output_length").reshape(B)
+    if max_total is None:
+        max_total = int(ol.max().item()) if B > 0 else 0
+    out = dict(out or {})
+    f32 = {"dtype": torch.float32, "name": "float32"}
+    risk = _buf(out, dev, "risk", (B,), **f32)
+    loss = _buf(out, dev, "loss", (B,), **f32)
+    gl = _buf(out, dev, "grad_logits", (B, T, D), want=need_grad, **f32)
+    gc = _buf(out, dev, "grad_cost", (B, T, D), want=need_grad, **f32)
+    wsb = int(lib.ssnt_v2_expected_cost_workspace_size(B, T, int(max_total), bool(test_mode),
+                                                       bool(need_grad)))
+    ws = _workspace(dev, wsb)
+    st = out.get("status")
+    if st is None:
+        st = _status(dev)
+    else:
+        st.zero_()
+    rc = lib.ssnt_v2_expected_cost_device(_p(lg), _p(cs), _p(table), _p(il), _p(ol), B, T, D,
+                                          int(max_total), int(zero_duration_id), bool(allow_skip),
+                                          bool(test_mode), _p(risk), _p(loss), _p(gl), _p(gc),
+                                          _p(ws), wsb, _p(st), _stream(dev))
+    _finish("v2_expected_cost", rc, st, check)
+    res = {"risk": risk, "loss": loss, "status": st}
+    if need_grad:
+        res["grad_logits"] = gl
+        res["grad_cost"] = gc
+    return res
+
+
+class V2ExpectedCost(torch.autograd.Function):
+    """Autograd wrapper of v2_expected_cost: per-utterance risk (B,), differentiable with respect
+    to logits and cost; the gradients come from the same call. The status word is checked in
+    backward, as V2DurationLoss does (check=False skips it)."""
+
+    @staticmethod
+    def forward(ctx, logits, cost, duration_table, input_length, output_length, zero_duration_id,
+                allow_skip=False, test_mode=False, max_total=None, check=True):
+        r = v2_expected_cost(logits.detach(), cost.detach(), duration_table, input_length,
+                             output_length, zero_duration_id, allow_skip=allow_skip,
+                             test_mode=test_mode, max_total=max_total,
+                             need_grad=logits.requires_grad or cost.requires_grad)
+        ctx.save_for_backward(r.get("grad_logits"), r.get("grad_cost"), r["status"])
+        ctx.check = check
+        return r["risk"]
+
+    @staticmethod
+    def backward(ctx, grad_risk):
+        gl, gc, st = ctx.saved_tensors
+        if ctx.check:
+            _finish("v2_expected_cost_loss", 0, st, True)
+        gr = grad_risk.to(torch.float32)[:, None, None]
+        need_l, need_c = ctx.needs_input_grad[:2]
+        dl = gl * gr if need_l and gl is not None else None
+        dc = gc * gr if need_c and gc is not None else None
+        return dl, dc, None, None, None, None, None, None, None, None
+
+
+def v2_expected_cost_loss(logits, cost, duration_table, input_length, output_length,
+                          zero_duration_id, allow_skip=False, test_mode=False, max_total=None,
+                          check=True):
+    """risk (B,) of ``v2_expected_cost``, differentiable in ``logits`` and ``cost`` (minimum-risk
+    training on durations, the expected final total in test mode)."""
+    return V2ExpectedCost.apply(logits, cost, duration_table, input_length, output_length,
+                                zero_duration_id, allow_skip, test_mode, max_total, check)
+
+
+def v2_duration_entropy(logits, duration_table, input_length, output_length, zero_duration_id,
+                        allow_skip=False, test_mode=False, max_total=None, check=True):
+    """The entropy H (B,) of the posterior over admissible duration-class sequences,
+    differentiable: H = ln Z - E[ln w(path)], with ln Z = -loss of ``v2_duration_loss`` and
+    E[ln w] = risk of ``v2_expected_cost_loss`` for cost = logits (a class whose logit is -inf
+    has weight zero, so its cost never counts). An utterance without an admissible path gets
+    -inf."""
+    cost = logits.to(torch.float32)
+    loss = v2_duration_loss(logits, duration_table, input_length, output_length, zero_duration_id,
+                            allow_skip, test_mode, max_total, False, check)
+    risk = v2_expected_cost_loss(logits, cost, duration_table, input_length, output_length,
+                                 zero_duration_id, allow_skip, test_mode, max_total, check)
+    return -loss - risk
 
 
 def lattice_beam_search_decode(lattice, input_length, beam_width, *, check=True):
