@@ -123,6 +123,10 @@ int ssnt_version(char *buf, size_t len);
  * steps >= S_b or positions >= P_b, the shift out of position P_b - 1, every entry of step
  * S_b - 1 but the terminal emit at (S_b - 1, P_b - 1) -- that one too without
  * SSNT_FLAG_TERMINAL_EMIT -- and the previous contents of the outputs and the workspace.
+ * Input domain of the cells that are read: a value below -1e6 and a NaN are exact zeros (as -inf),
+ * a value above +1e6 is clamped to +1e6, and the results are specified only while every partial
+ * log-probability (log alpha, log beta, ln Z) stays above about -2^29 ln 2 = -3.7e8 (DESIGN.md 3
+ * "Input domain").
  * Device variant: all pointers are device pointers; `stream` is a hipStream_t (NULL = legacy
  * default); `workspace` must hold ssnt_fwd_bwd_workspace_size() bytes -- always take the size
  * from that query, never compute it: it is 0 (NULL workspace) when every row of the dispatched

@@ -5,10 +5,12 @@ Pure numpy; the float64 reference is tests/expected_cost_ref.py. Test infrastruc
 import numpy as np
 
 import expected_cost_ref as R
+import value_cases as VC
 
 LANE_US = (1, 2, 63, 64, 65, 128, 129, 257, 513, 1024)
 CHUNK_US = (5, 130)
 OUTPUTS = ("risk", "loss", "grad_trans", "grad_cost", "grad_obs")
+VALUE_NAMES = [f"value-{n}" for n in VC.TOLERANCE_CLASSES]
 
 
 def lattice(B, T, U, seed, obs=False):
@@ -71,6 +73,16 @@ def cancellation():
     return c
 
 
+def value(name):
+    """One input value class of tests/value_cases.py (its TOLERANCE_CLASSES) at B=4, T=48, U=20:
+    ragged lengths, S mod 4 = 0, 3, 2, 1; the costs are the usual N(0, 1)."""
+    B, T, U = 4, 48, 20
+    S, _ = VC.lengths(B, T, U)
+    c = make(B, T, U, 48, obs=False, S=S, P=[20, 13, 7, 12])
+    c["lt"] = VC.lattice(name, c["lt"])
+    return c
+
+
 def case_makers(chunk_rows):
     """name -> function making the case, for every shape the GPU tests compare with the reference;
     chunk_rows(U, obs) is the sweep's chunk depth (ssnt_expected_cost_chunk_rows of the A/B
@@ -87,6 +99,8 @@ def case_makers(chunk_rows):
             out[f"mode-obs{int(obs)}-term{int(terminal)}"] = lambda obs=obs, terminal=terminal: mode(obs, terminal)
     out["exponent"] = exponent
     out["cancellation"] = cancellation
+    for name in VC.TOLERANCE_CLASSES:
+        out[f"value-{name}"] = lambda name=name: value(name)
     return out
 
 

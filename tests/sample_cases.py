@@ -6,6 +6,7 @@ import functools
 import numpy as np
 
 import sample_ref as SR
+import value_cases as VC
 
 LANE_WIDTHS = [1, 2, 63, 64, 65, 127, 128, 129, 256, 257, 512, 513, 1024]
 CHUNK_STEPS = [31, 32, 33, 64, 65, 97]
@@ -124,6 +125,17 @@ def reuse():
     return _case(lt, lo, [40, 33, 40, 12, 25], [40, 20, 1, 12, 25], 8, 12)
 
 
+@functools.lru_cache(maxsize=None)
+def value(name):
+    """One input value class of tests/value_cases.py (its TOLERANCE_CLASSES) at B=4, T=48, U=20 with
+    16 samples: ragged lengths, S mod 4 = 0, 3, 2, 1. The float64 reference does not depend on the
+    distribution; tests/test_value_cases_ref.py holds every case to the cap on the CPU."""
+    B, T, U = 4, 48, 20
+    lt, _ = lattice(B, T, U, 48)
+    S, _ = VC.lengths(B, T, U)
+    return _case(VC.lattice(name, lt), None, S, [20, 13, 7, 12], 16, 7)
+
+
 def capped(lib):
     """(name, case) of every case whose unclear share the GPU test holds to the cap."""
     Tl = switch_T(lib)
@@ -134,6 +146,7 @@ def capped(lib):
     out += [(f"switch{T}", switch(T)) for T in (Tl, Tl + 1)]
     out += [("single long row", single_long_row())]
     out += [("zero", zero_probability()), ("frequency", frequency()), ("reuse", reuse())]
+    out += [(f"value {n}", value(n)) for n in VC.TOLERANCE_CLASSES]
     return out
 
 

@@ -123,6 +123,24 @@ def test_infeasible_rule_and_scale():
     assert R.scale(np.zeros((6, 4, 2)), 6, 4, True) == 1.0
 
 
+def test_value_cases_keep_the_reference_well_defined():
+    # the input value classes the GPU test adds (tests/expected_cost_cases.py `value`): the float64
+    # log-domain DP is feasible and finite on each, keeps both identities, and its normaliser is the
+    # one of the tame distribution (`scale` is a function of the costs and the extents only)
+    import expected_cost_cases as EC
+    tame = EC.reference(EC.make(4, 48, 20, 48, obs=False, S=EC.value("peaked30")["S"], P=[20, 13, 7, 12]))
+    for name in EC.VALUE_NAMES:
+        assert name in EC.case_makers(lambda U, obs: 8)
+        c = EC.value(name[len("value-"):])
+        r = EC.reference(c)
+        assert r["feasible"].all() and np.array_equal(r["scale"], tame["scale"]), name
+        for k in ("risk", "loss", "grad_trans", "grad_cost"):
+            assert np.isfinite(r[k]).all(), (name, k)
+        for b, S in enumerate(c["S"]):
+            assert np.abs(r["grad_cost"][b, :S - 1].sum(axis=(1, 2)) - 1.0).max() < 1e-9, name
+            assert np.abs(r["grad_trans"][b, :S - 1].sum(axis=(1, 2))).max() < 1e-9 * r["scale"][b], name
+
+
 def test_underflow_safe():
     S, P, T, U = 300, 40, 300, 40
     lt, cost, lo = _case(11, T, U, False)

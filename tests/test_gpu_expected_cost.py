@@ -132,6 +132,18 @@ def test_exponent_range_and_cancellation(gpu, name):
     _check(got, _ref(name), c, name)
 
 
+@pytest.mark.parametrize("name", EC.VALUE_NAMES)
+def test_value_classes(gpu, name):
+    # saturated, positive, exponent-heavy and alternating log_trans (tests/value_cases.py) within
+    # the tolerances every other case holds
+    c = _case(name)
+    got = _run(gpu, c)
+    for k in EC.OUTPUTS:
+        if k in got:
+            assert np.isfinite(got[k]).all(), k
+    _check(got, _ref(name), c, name)
+
+
 @pytest.mark.parametrize("name", ["lane-65", "lane-513", "mode-obs1-term1", "mode-obs0-term0", "exponent",
                                   "chunk-5-3", "chunk-130-2"])
 def test_value_only_same_bits(gpu, name):

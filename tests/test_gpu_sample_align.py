@@ -11,6 +11,7 @@ import torch
 
 import sample_cases as SC
 import sample_ref as SR
+import value_cases as VC
 
 pytestmark = pytest.mark.gpu
 
@@ -116,6 +117,14 @@ def test_exponent_range(gpu):
     assert np.all(np.isfinite(g["log_prob"])) and np.all(g["log_prob"] < -104)
     _check(c, g, cap=False, where="exponent range")
     assert c["ref"]["clear"].any()
+
+
+@pytest.mark.parametrize("name", VC.TOLERANCE_CLASSES)
+def test_value_classes(gpu, name):
+    # saturated, positive, exponent-heavy and alternating inputs (tests/value_cases.py): the same
+    # checks as every other case, the cap included
+    c = SC.value(name)
+    _check(c, _run(gpu, c), where=f"value {name}")
 
 
 def test_zero_probability_transitions(gpu):

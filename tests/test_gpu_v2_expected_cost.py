@@ -144,6 +144,18 @@ def test_exponent_range_cancellation_and_constant_cost(gpu, name):
         assert np.all(got["loss"] > 80.0 * c["I"])  # far outside the f32 exponent range
 
 
+@pytest.mark.parametrize("name", EC.VALUE_NAMES)
+def test_value_classes(gpu, name):
+    # saturated, positive, exponent-heavy and alternating logits (tests/value_cases.py), band and
+    # test mode, within the tolerances every other case holds
+    c = _case(name)
+    got = _run(gpu, c, check=True)
+    for k in EC.OUTPUTS:
+        assert np.isfinite(got[k]).all(), k
+    _check(got, _ref(name), c, name)
+    assert _ref(name)["feasible"].all()
+
+
 # ---- 2. cross-checks against v2_fwd_bwd; the value-only form ------------------------------------
 CROSS = (["mode-test0-skip0", "mode-test0-skip1", "mode-test1-skip0", "mode-test1-skip1", "long-test0",
           "long-test1", "wide"] + _names("chunk-"))

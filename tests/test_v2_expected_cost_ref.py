@@ -108,5 +108,14 @@ def test_the_shared_cases_are_what_the_issue_lists():
     assert {f"chunk-4-{I}" for I in (1, 2, 63, 64, 65, 129)} <= names
     assert {f"chunk-40-{I}" for I in (1, 2, 31, 32, 33, 65)} <= names
     assert {"wide", "long-test0", "long-test1", "infeasible", "exponent", "cancellation", "constant"} <= names
+    assert set(C.VALUE_NAMES) <= names and len(C.VALUE_NAMES) == 12
+    for name in C.VALUE_NAMES:  # the float64 reference is feasible and finite on every value class
+        c = C.case_makers(lambda D: 64)[name]()
+        r = C.reference(c)
+        assert r["feasible"].all(), name
+        assert all(np.isfinite(r[k]).all() for k in ("risk", "loss", "grad_logits", "grad_cost", "scale")), name
+        n = c["I"]
+        for b in range(len(n)):
+            assert np.allclose(r["grad_cost"][b, :n[b]].sum(axis=1), 1.0, atol=TOL), name
     w = C.wide()
     assert w["test_mode"] and w["logits"].shape[1:] == (48, 16) and w["mt"] + 1 > 512

@@ -110,6 +110,15 @@ def test_redrawn_uniforms_leave_the_family_clear(name):
     assert np.array_equal(u, u2) and np.array_equal(res["duration_class"], res2["duration_class"])
 
 
+def test_value_families_are_the_tolerance_classes():
+    import value_cases as VC
+    assert SR.VALUE_CLASSES == VC.TOLERANCE_CLASSES
+    for n in VC.TOLERANCE_CLASSES:
+        for mode in ("band", "test_mode"):
+            case, K, _, res = SR.family(f"value-{n}-{mode}")
+            assert K == 16 and case[0].shape == (4, 32, 8) and res["feasible"].all(), (n, mode)
+
+
 def _family_of(name):  # the tiny cases are one family per mode, over their six seeds
     return re.sub(r"^tiny-\d+-", "tiny-", name)
 

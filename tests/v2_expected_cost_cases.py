@@ -6,6 +6,7 @@ import numpy as np
 
 import f4_cases
 import v2_expected_cost_ref as R
+import value_cases as VC
 
 CLASS_DS = (1, 3, 8, 9, 16, 17, 33, 64)   # every instantiation of the class count and its padding
 CHUNK_DS = (4, 40)                        # 64-step and 32-step staging chunks
@@ -122,6 +123,16 @@ def constant():
     return c
 
 
+def value(name, test_mode):
+    """One input value class of tests/value_cases.py (its TOLERANCE_CLASSES) on the teacher-forced
+    logits of v2_sample_ref.value_case: B=4, I=32 ragged, D=8, durations 0..7; costs N(0, 1)."""
+    import v2_sample_ref
+    logits, table, I, O, mt, allow_skip, tm = v2_sample_ref.value_case(name, test_mode)
+    return make(logits, I, O, table, mt=mt, allow_skip=allow_skip, test_mode=tm, seed=32)
+
+
+VALUE_NAMES = [f"value-{n}-test{tm}" for n in VC.TOLERANCE_CLASSES for tm in (0, 1)]
+
 MODES = {"band": (False, True), "test_mode": (True, True), "band-noskip": (False, False),
          "test_mode-noskip": (True, False)}  # name -> (test_mode, allow_skip)
 
@@ -156,6 +167,9 @@ def case_makers(chunk_steps):
     out["exponent"] = exponent
     out["cancellation"] = cancellation
     out["constant"] = constant
+    for n in VC.TOLERANCE_CLASSES:
+        for tm in (0, 1):
+            out[f"value-{n}-test{tm}"] = lambda n=n, tm=tm: value(n, bool(tm))
     return out
 
 

@@ -271,6 +271,24 @@ for _mode in ("band", "test_mode"):
 FAMILIES["i12d64-test_mode"] = (8, functools.partial(_random_family, 12, 12, 64, np.arange(64), "test_mode"))
 
 
+def value_case(name, test_mode, B=4, Imax=32, D=8):
+    """One input value class of tests/value_cases.py on teacher-forced logits (B=4, I=32 ragged,
+    D=8, durations 0..7, O the planted durations' sum, so a path inside the band exists)."""
+    import oracle as O
+    import value_cases as VC
+    d = O.synth_durations(B, Imax, 4 * Imax, D, seed=32)
+    logits = VC.v2(name, O.synth_v2_step_logits(d, D, seed=33))
+    I = np.array([Imax, Imax - 5, Imax - 2, Imax - 11], np.int32)
+    Ol = np.array([int(d[b, :I[b]].sum()) for b in range(B)], np.int32)
+    return logits, np.arange(D, dtype=np.int32), I, Ol, int(Ol.max()) + (20 if test_mode else 0), True, bool(test_mode)
+
+
+VALUE_CLASSES = ("peaked30", "saturated_emit", "plus88", "minus1e4", "alt_rows", "alt_cols")  # = VC.TOLERANCE_CLASSES
+for _name in VALUE_CLASSES:
+    for _mode in ("band", "test_mode"):
+        FAMILIES[f"value-{_name}-{_mode}"] = (16, functools.partial(value_case, _name, _mode == "test_mode"))
+
+
 @functools.lru_cache(maxsize=None)
 def family(name, seed=0):
     """(case, K, u, reference result) of one family, computed once."""
