@@ -295,6 +295,33 @@ int ssnt_expected_cost_device(const float *log_trans, const float *log_obs, cons
                               float *grad_trans, float *grad_cost, float *grad_obs,
                               void *workspace, size_t workspace_bytes, int *status, void *stream);
 
+/* ---- the posterior duration distribution on the emit/shift lattice ----
+ * Over the tensors of ssnt_fwd_bwd_device: the duration of position p on a path is the number of
+ * steps s with position[s] = p (>= 1 for every p < P_b). dur_post (B, max_pos, num_bins) f32, the
+ * bin index being the duration: dur_post[b,p,d] = P(d_p = d | log_trans, log_obs) for
+ * d < num_bins-1 (bin 0 an exact 0), and dur_post[b,p,num_bins-1] = P(d_p >= num_bins-1), the tail,
+ * formed by its own sum and never as one minus the rest; a row p < P_b sums to 1. loss (B) = -ln Z
+ * with the bits of ssnt_expected_cost_device's loss; it may be NULL. 2 <= num_bins <= 256 and no
+ * flag but SSNT_FLAG_TERMINAL_EMIT, else SSNT_ERR_INVALID_ARG, as for a NULL dur_post. Every
+ * element of dur_post is written: rows p >= P_b are 0, every bin d > S_b-P_b+1 is an exact 0 (no
+ * position can hold more steps), a zero term contributes an exact 0 (with one live path every bin
+ * off its durations is +0), and an infeasible utterance (S_b < P_b, S_b = 0, P_b = 0, Z = 0, or a
+ * length beyond the tensor, which also sets SSNT_ERR_BAD_LENGTH in `status`) gets dur_post 0 and
+ * loss +inf. -inf in log_trans / log_obs is legal; the cells ssnt_fwd_bwd_device never reads into a
+ * result are never read into one here. Sums run in step order without atomics: the same bits on
+ * every call, alone or in any batch. max_pos > 1024 returns SSNT_ERR_UNSUPPORTED, as does a
+ * log_trans not 8-byte aligned. `workspace` holds ssnt_duration_posterior_workspace_size() bytes,
+ * 8-byte aligned (alpha's and beta's rows, 8 B per cell and direction; a function of the shape
+ * alone, 0 for a shape the call refuses); missing or short: SSNT_ERR_WORKSPACE. A refused call
+ * writes nothing. Device pointers, asynchronous on `stream`. New: the reference has no posterior
+ * over durations. */
+size_t ssnt_duration_posterior_workspace_size(int batch, int max_steps, int max_pos, int num_bins);
+int ssnt_duration_posterior_device(const float *log_trans, const float *log_obs,
+                                   const int *step_len, const int *pos_len, int batch,
+                                   int max_steps, int max_pos, int num_bins, int flags,
+                                   float *dur_post, float *loss, void *workspace,
+                                   size_t workspace_bytes, int *status, void *stream);
+
 /* ---- F4: v2 duration-class (semi-Markov) forward-backward (DESIGN.md
  * "Duration lattice"). New: the reference only decodes this lattice; the move rules are the v2
  * decode's (src/v2.rs:94-166 -- band, overrun, exact final total, zero-duration class; test_mode

@@ -41,6 +41,14 @@ int ssnt_v2_sample_align_form(int cone, int launches);
  * launch; 3 default: timing one launch over a workspace an earlier full call left) */
 int ssnt_expected_cost_chunk_rows(int max_pos, int has_obs);
 int ssnt_expected_cost_launches(int mask);
+/* duration posterior: the step rows of one staged chunk (low 16 bits) and the positions of one
+ * workgroup's tile (the bits above) of the duration launch for a shape, the transition rows of one
+ * chunk of its sweeps, which stage no cost (host queries; 0 for a shape the call does not take),
+ * and the launches that run (bit 0 the sweeps, bit 1 the duration launch; 3 default: timing one
+ * launch over a workspace an earlier full call left) */
+int ssnt_duration_posterior_block(int max_pos, int num_bins, int has_obs);
+int ssnt_duration_posterior_sweep_rows(int max_pos, int has_obs);
+int ssnt_duration_posterior_launches(int mask);
 /* expected duration-path cost: the sweep steps of one staged chunk for a class count (host query;
  * 0 beyond 64 classes), and the launches of the full call that run (bit 0 the sweeps, bit 1 the
  * gradient launch; 3 default: timing one launch over a workspace an earlier full call left) */

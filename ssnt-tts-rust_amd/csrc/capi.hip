@@ -707,6 +707,15 @@ int ssnt_expected_cost_chunk_rows(int max_pos, int has_obs) {
   return expected_cost_chunk_rows(max_pos, has_obs != 0);
 }
 int ssnt_expected_cost_launches(int mask) { return set_expected_cost_launches(mask); }
+int ssnt_duration_posterior_block(int max_pos, int num_bins, int has_obs) {
+  if (max_pos < 1 || max_pos > 1024 || num_bins < 2 || num_bins > 256) return 0;
+  return duration_posterior_block(max_pos, num_bins, has_obs != 0);
+}
+int ssnt_duration_posterior_sweep_rows(int max_pos, int has_obs) {
+  if (max_pos < 1 || max_pos > 1024) return 0;
+  return alpha_beta_chunk_rows(max_pos, has_obs != 0);
+}
+int ssnt_duration_posterior_launches(int mask) { return set_duration_posterior_launches(mask); }
 int ssnt_v2_expected_cost_chunk_steps(int duration_class_size) {
   if (duration_class_size < 1 || duration_class_size > 64) return 0;
   return v2_expected_cost_chunk_steps(duration_class_size);
@@ -873,6 +882,24 @@ int ssnt_expected_cost_device(const float* log_trans, const float* log_obs, cons
   a.grad_obs = grad_obs; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
   a.status = status;
   return launch_expected_cost(a, as_stream(stream));
+}
+
+size_t ssnt_duration_posterior_workspace_size(int batch, int max_steps, int max_pos, int num_bins) {
+  if (batch <= 0 || max_steps < 0 || max_pos < 0 || max_pos > 1024 || num_bins < 2 || num_bins > 256) return 0;
+  return duration_posterior_workspace_bytes(batch, max_steps, max_pos, num_bins);
+}
+
+int ssnt_duration_posterior_device(const float* log_trans, const float* log_obs, const int* step_len,
+                                   const int* pos_len, int batch, int max_steps, int max_pos,
+                                   int num_bins, int flags, float* dur_post, float* loss,
+                                   void* workspace, size_t workspace_bytes, int* status,
+                                   void* stream) {
+  DurationPosteriorArgs a{};
+  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
+  a.B = batch; a.T = max_steps; a.U = max_pos; a.D = num_bins; a.flags = flags;
+  a.dur_post = dur_post; a.loss = loss; a.workspace = workspace;
+  a.workspace_bytes = workspace_bytes; a.status = status;
+  return launch_duration_posterior(a, as_stream(stream));
 }
 
 size_t ssnt_v2_fwd_bwd_workspace_size(int batch, int max_steps, int max_total, bool test_mode) {

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "align_dev.h"
+#include "ec_rows.h"
 
 namespace ssnt {
 namespace {
@@ -30,44 +31,36 @@ namespace {
 constexpr int kEcJunk = 64;  // elements behind each buffer, for unused units' writes: lane (< 64)
 constexpr int kEcGradThreads = 256;
 constexpr int kEcGradCells = 4096;     // cells per workgroup of the gradient launch, about
-constexpr size_t kEcHeadRec = 16;      // workspace head per utterance: Z.m, Z.e, risk, 0
 
 struct EcLayout {
   int K, R;
   size_t base_off, total;  // bytes
 };
-// two chunk buffers each of (E, Sh) as xf, the cost pair, and O as xf
-inline EcLayout ec_layout(int U, int R, bool obs) {
+// two chunk buffers each of (E, Sh) as xf, the cost pair (with the mean only), and O as xf
+inline EcLayout ec_layout(int U, int R, bool obs, bool mean = true) {
   EcLayout L{};
   L.K = aln_k(U);
   L.R = R;
   const size_t buf = (size_t)R * L.K * aln_kstride(L.K) + kEcJunk;  // elements of one buffer
   L.base_off = kAlnHeadBytes;
-  L.total = L.base_off + 2 * buf * (16 + 8 + (obs ? 8 : 0));
+  L.total = L.base_off + 2 * buf * (16 + (mean ? 8 : 0) + (obs ? 8 : 0));
   return L;
 }
-inline EcLayout ec_pick(int U, bool obs) {
-  return aln_pick(aln_chunk_rows((U + 63) / 64), 1, [&](int r) { return ec_layout(U, r, obs); });
-}
-// stored rows are padded to whole lane slices
-inline int ec_upad(int U) {
-  const int K = aln_k(U);
-  return (U + K - 1) / K * K;
+inline EcLayout ec_pick(int U, bool obs, bool mean = true) {
+  return aln_pick(aln_chunk_rows((U + 63) / 64), 1, [&](int r) { return ec_layout(U, r, obs, mean); });
 }
 inline size_t ec_rows_bytes(int B, int T, int U) { return (size_t)B * T * ec_upad(U) * 12; }
-// the rows start at the first 16-byte boundary behind the head (the workspace itself: 8-byte aligned)
-__host__ __device__ inline float* ec_rows_base(void* ws, int B) {
-  const uintptr_t p = reinterpret_cast<uintptr_t>(ws) + (size_t)B * kEcHeadRec;
-  return reinterpret_cast<float*>((p + 15) & ~(uintptr_t)15);
-}
 
 struct EcParams {
   int R, Up;
   unsigned base_off;
 };
 
-template <int K, bool OBS, bool GRAD>
+// MEAN == false (GRAD only): alpha and beta alone, for the duration posterior: no
+// cost load, no mean arithmetic, no mean plane (m, e: 8 B per cell and direction), no risk.
+template <int K, bool OBS, bool GRAD, bool MEAN = true>
 __global__ __launch_bounds__(kAlnThreads) void k_expected_cost_sweep(ExpectedCostArgs a, EcParams q) {
+  constexpr int kPl = MEAN ? 3 : 2;  // planes of a stored row
   constexpr int kKs = aln_kstride(K);
   constexpr int kRow = K * kKs;  // LDS row stride in cells
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -82,14 +75,14 @@ __global__ __launch_bounds__(kAlnThreads) void k_expected_cost_sweep(ExpectedCos
   const int P = a.pos_len[b];
   const size_t TU = (size_t)T * U;
   const float* lt = a.log_trans + (size_t)b * TU * 2;
-  const float* cs = a.cost + (size_t)b * TU * 2;
+  const float* cs = MEAN ? a.cost + (size_t)b * TU * 2 : nullptr;
   const float* lo = OBS ? a.log_obs + (size_t)b * TU : nullptr;
   const bool term = (a.flags & SSNT_FLAG_TERMINAL_EMIT) != 0;
   float* head = GRAD ? reinterpret_cast<float*>(a.workspace) + (size_t)b * 4 : nullptr;
 
   auto publish = [&](xf Z, float risk) {  // one lane
     const bool none = Z.m == 0.0f;
-    a.risk[b] = none ? 0.0f : risk;
+    if constexpr (MEAN) a.risk[b] = none ? 0.0f : risk;
     if (a.loss) a.loss[b] = none ? __builtin_inff() : 0.0f - xf_log(Z);
     if constexpr (GRAD) {
       head[0] = Z.m;
@@ -108,13 +101,13 @@ __global__ __launch_bounds__(kAlnThreads) void k_expected_cost_sweep(ExpectedCos
   unsigned char* dbase = smem + q.base_off;
   float4* ltb = reinterpret_cast<float4*>(dbase);
   float2* ccb = reinterpret_cast<float2*>(dbase + (size_t)2 * bufsz * 16);
-  float2* obb = reinterpret_cast<float2*>(dbase + (size_t)2 * bufsz * 24);
-  float* rows = GRAD ? ec_rows_base(a.workspace, a.B) + ((size_t)dir * a.B + b) * T * Up * 3 : nullptr;
+  float2* obb = reinterpret_cast<float2*>(dbase + (size_t)2 * bufsz * (MEAN ? 24 : 16));
+  float* rows = GRAD ? ec_rows_base(a.workspace, a.B) + ((size_t)dir * a.B + b) * T * Up * kPl : nullptr;
 
   // ------------------------------------------------------------------ loaders
   const int NC = (S - 1 + R - 1) / R;  // chunks of transition rows 0..S-2, in either direction
   int goff[kAlnUnits], loff[kAlnUnits];
-  f32x2 lreg[kAlnUnits], creg[kAlnUnits];
+  f32x2 lreg[kAlnUnits], creg[MEAN ? kAlnUnits : 1];
   float oreg[OBS ? kAlnUnits : 1];
   if (loader) {
     const int w = wave - 1;
@@ -132,15 +125,17 @@ __global__ __launch_bounds__(kAlnThreads) void k_expected_cost_sweep(ExpectedCos
     const int r0 = chunk_first(c);
     const int n = chunk_count(c);
     const __amdgpu_buffer_rsrc_t rs = brsrc(lt + (size_t)r0 * U * 2, (unsigned)(n * U) * 8u);
-    const __amdgpu_buffer_rsrc_t rc = brsrc(cs + (size_t)r0 * U * 2, (unsigned)(n * U) * 8u);
+    const __amdgpu_buffer_rsrc_t rc = brsrc(MEAN ? cs + (size_t)r0 * U * 2 : nullptr, (unsigned)(n * U) * 8u);
     static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
       constexpr int u = decltype(Ic)::value;
       lreg[u] = rbuf_ld2(rs, goff[u], 0, 0);
     });
-    static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
-      constexpr int u = decltype(Ic)::value;
-      creg[u] = rbuf_ld2(rc, goff[u], 0, 0);
-    });
+    if constexpr (MEAN) {
+      static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
+        constexpr int u = decltype(Ic)::value;
+        creg[u] = rbuf_ld2(rc, goff[u], 0, 0);
+      });
+    }
     if constexpr (OBS) {
       const __amdgpu_buffer_rsrc_t ro = brsrc(lo + (size_t)(r0 + 1) * U, (unsigned)(n * U) * 4u);
       static_for<kAlnUnits>([&](auto Ic) __attribute__((always_inline)) {
@@ -159,7 +154,7 @@ __global__ __launch_bounds__(kAlnThreads) void k_expected_cost_sweep(ExpectedCos
       int ee, es;
       xf_exp_pair(lreg[u].x, lreg[u].y, true, true, me, ee, ms, es);
       dst[loff[u]] = make_float4(me, __builtin_bit_cast(float, ee), ms, __builtin_bit_cast(float, es));
-      dstc[loff[u]] = make_float2(creg[u].x, creg[u].y);
+      if constexpr (MEAN) dstc[loff[u]] = make_float2(creg[u].x, creg[u].y);
     });
     if constexpr (OBS) {
       float2* dsto = obb + (size_t)(c & 1) * bufsz;
@@ -191,18 +186,18 @@ __global__ __launch_bounds__(kAlnThreads) void k_expected_cost_sweep(ExpectedCos
     const size_t at = ((size_t)(S - 1) * U + (P - 1)) * 2;
     const xf e = xf_exp(lt[at], true);
     Et = xf_norm(e.m, e.e);
-    ct = cs[at];
+    if constexpr (MEAN) ct = cs[at];
   }
   auto store_row = [&](int s) __attribute__((always_inline)) {
     if constexpr (GRAD) {
       if (K * lane < Up) {
-        float* dst = rows + (size_t)s * Up * 3 + K * lane;
+        float* dst = rows + (size_t)s * Up * kPl + K * lane;
         float ev[K];
 #pragma unroll
         for (int j = 0; j < K; ++j) ev[j] = __builtin_bit_cast(float, Xe[j]);
         st_vec<K>(dst, Xm);
         st_vec<K>(dst + Up, ev);
-        st_vec<K>(dst + 2 * Up, Mn);
+        if constexpr (MEAN) st_vec<K>(dst + 2 * Up, Mn);
       }
     }
   };
@@ -255,27 +250,32 @@ __global__ __launch_bounds__(kAlnThreads) void k_expected_cost_sweep(ExpectedCos
 #pragma unroll
           for (int j = 0; j < K; ++j) {
             const float4 t = Bf[i * kRow + j * kKs];
-            const float2 cc = CB[i * kRow + j * kKs];
             sm[j] = Xm[j] * t.x;
             se[j] = Xe[j] + __builtin_bit_cast(int, t.y);
             hm[j] = Xm[j] * t.z;
             he[j] = Xe[j] + __builtin_bit_cast(int, t.w);
-            xs[j] = Mn[j] + cc.x;
-            xh[j] = Mn[j] + cc.y;
+            if constexpr (MEAN) {
+              const float2 cc = CB[i * kRow + j * kKs];
+              xs[j] = Mn[j] + cc.x;
+              xh[j] = Mn[j] + cc.y;
+            }
           }
           const float lm = shr1(hm[K - 1]);
           const int le = shr1(he[K - 1]);
-          const float lx = shr1(xh[K - 1]);
+          float lx = 0.0f;
+          if constexpr (MEAN) lx = shr1(xh[K - 1]);
 #pragma unroll
           for (int j = 0; j < K; ++j) {
             const float xm = (j == 0) ? lm : hm[j > 0 ? j - 1 : 0];
             const int xe = (j == 0) ? le : he[j > 0 ? j - 1 : 0];
-            const float xx = (j == 0) ? lx : xh[j > 0 ? j - 1 : 0];
             const int em = max(se[j], xe);
             const float t1 = xldexp(sm[j], se[j] - em);
             const float t2 = xldexp(xm, xe - em);
             const float tt = t1 + t2;
-            Mn[j] = mean_of(t1, xs[j], t2, xx, tt);
+            if constexpr (MEAN) {
+              const float xx = (j == 0) ? lx : xh[j > 0 ? j - 1 : 0];
+              Mn[j] = mean_of(t1, xs[j], t2, xx, tt);
+            }
             float sum = tt;
             int ee = em;
             if constexpr (OBS) {
@@ -308,15 +308,14 @@ __global__ __launch_bounds__(kAlnThreads) void k_expected_cost_sweep(ExpectedCos
           }
           const float rm = shl1(qm[0]);
           const int re = shl1(qe[0]);
-          const float rx = shl1(bn[0]);
+          float rx = 0.0f;
+          if constexpr (MEAN) rx = shl1(bn[0]);
 #pragma unroll
           for (int j = 0; j < K; ++j) {
             const int p = K * lane + j;
             const float ym = (j == K - 1) ? rm : qm[j + 1 < K ? j + 1 : 0];
             const int ye = (j == K - 1) ? re : qe[j + 1 < K ? j + 1 : 0];
-            const float yx = (j == K - 1) ? rx : bn[j + 1 < K ? j + 1 : 0];
             const float4 t = Bf[i * kRow + j * kKs];
-            const float2 cc = CB[i * kRow + j * kKs];
             const float u1m = t.x * qm[j];
             const int u1e = __builtin_bit_cast(int, t.y) + qe[j];
             // (the shift out of P-1 is masked, exponent included: what stands at p+1 = P may be
@@ -328,7 +327,12 @@ __global__ __launch_bounds__(kAlnThreads) void k_expected_cost_sweep(ExpectedCos
             const float t1 = xldexp(u1m, u1e - em);
             const float t2 = xldexp(u2m, u2e - em);
             const float tt = t1 + t2;
-            const float mn = mean_of(t1, bn[j] + cc.x, t2, yx + cc.y, tt);
+            float mn = 0.0f;
+            if constexpr (MEAN) {
+              const float yx = (j == K - 1) ? rx : bn[j + 1 < K ? j + 1 : 0];
+              const float2 cc = CB[i * kRow + j * kKs];
+              mn = mean_of(t1, bn[j] + cc.x, t2, yx + cc.y, tt);
+            }
             const xf nv = xf_norm(tt, em);
             const bool live = p < P;
             Xm[j] = live ? nv.m : 0.0f;
@@ -451,7 +455,32 @@ int launch_sweep_k(const ExpectedCostArgs& a, const EcLayout& L, bool grad, hipS
                     a, q);
 }
 
+template <int K, bool OBS>
+int launch_ab_sweep_k(const ExpectedCostArgs& a, const EcLayout& L, hipStream_t st) {
+  const EcParams q{L.R, ec_upad(a.U > 0 ? a.U : 1), (unsigned)L.base_off};
+  return launch_lds(k_expected_cost_sweep<K, OBS, true, false>, dim3(2 * a.B), dim3(kAlnThreads), L.total,
+                    kLdsBudget, st, a, q);
+}
+
 }  // namespace
+
+size_t alpha_beta_rows_workspace_bytes(int B, int T, int U) {
+  return (size_t)B * kEcHeadRec + 16 + 2 * (size_t)B * T * ec_upad(U) * 8;
+}
+
+int alpha_beta_chunk_rows(int U, bool obs) { return ec_pick(U > 0 ? U : 1, obs, false).R; }
+
+// The caller has made launch_expected_cost's checks (B, T, U >= 1, U <= 1024, flags, pointers,
+// alignment, the 32-bit offsets) and holds a workspace of alpha_beta_rows_workspace_bytes().
+int launch_alpha_beta_sweep(const ExpectedCostArgs& a, hipStream_t st) {
+  const bool obs = a.log_obs != nullptr;
+  const EcLayout L = ec_pick(a.U > 0 ? a.U : 1, obs, false);  // (U == 0: every utterance is infeasible)
+  if (L.total > kLdsBudget || a.B > kAlnNoUnit / 2) return SSNT_ERR_UNSUPPORTED;
+  return aln_with_k(L.K, [&](auto Kc) {
+    constexpr int K = decltype(Kc)::value;
+    return obs ? launch_ab_sweep_k<K, true>(a, L, st) : launch_ab_sweep_k<K, false>(a, L, st);
+  });
+}
 
 size_t expected_cost_workspace_bytes(int B, int T, int U) {
   return (size_t)B * kEcHeadRec + 16 + 2 * ec_rows_bytes(B, T, U);

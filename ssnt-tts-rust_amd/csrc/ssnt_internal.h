@@ -160,6 +160,35 @@ int launch_expected_cost(const ExpectedCostArgs& a, hipStream_t stream);
 int expected_cost_chunk_rows(int U, bool obs);
 int set_expected_cost_launches(int mask);
 #endif
+// the same sweeps without the mean (expected_cost.hip): alpha and beta rows (m, e: 8 B per cell and
+// direction), Z and loss into a workspace of alpha_beta_rows_workspace_bytes(); cost, risk and the
+// gradient pointers of `a` are not read. The caller has made launch_expected_cost's checks.
+size_t alpha_beta_rows_workspace_bytes(int B, int T, int U);
+int alpha_beta_chunk_rows(int U, bool obs);
+int launch_alpha_beta_sweep(const ExpectedCostArgs& a, hipStream_t stream);
+
+// ---- the posterior duration distribution on the emit/shift lattice (duration_posterior.hip) ----
+struct DurationPosteriorArgs {
+  const float* log_trans;  // (B,T,U,2)
+  const float* log_obs;    // (B,T,U) or null
+  const int* step_len;     // (B)
+  const int* pos_len;      // (B)
+  int B, T, U, D, flags;   // D: bins, 2..256; bin d < D-1 is P(d_p = d), bin D-1 the tail P(d_p >= D-1)
+  float* dur_post;    // (B,U,D)
+  float* loss;        // (B) or null
+  void* workspace;    // Z per utterance, then both chains' rows
+  size_t workspace_bytes;
+  int* status;
+};
+size_t duration_posterior_workspace_bytes(int B, int T, int U, int D);
+int launch_duration_posterior(const DurationPosteriorArgs& a, hipStream_t stream);
+#ifdef SSNT_AB
+// the step rows of one staged chunk and the positions of one workgroup's tile for this shape
+// (rows in the low 16 bits, positions above), and which launches run (bit 0 the sweeps, bit 1 the
+// duration launch; 3 default); the sweeps' chunk depth is alpha_beta_chunk_rows
+int duration_posterior_block(int U, int D, bool obs);
+int set_duration_posterior_launches(int mask);
+#endif
 
 // ---- F4: v2 duration-class forward-backward (v2_fwd_bwd.hip) ----
 struct V2FwdBwdArgs {

@@ -8,7 +8,9 @@ fallback. Added beside them: the lattice forward-backward (``ssnt_fwd_bwd``,
 ``SSNTLatticeLoss``), the exact best path over the same lattice (``ssnt_viterbi_align``),
 the exact N best alignments (``ssnt_nbest_align``), alignments drawn from its posterior
 (``ssnt_sample_align``), the posterior expectation of an additive path cost with its gradients
-(``ssnt_expected_cost``, ``SSNTExpectedCost``, ``ssnt_alignment_entropy``), the counterparts of the first three on the v2
+(``ssnt_expected_cost``, ``SSNTExpectedCost``, ``ssnt_alignment_entropy``), the posterior
+distribution of every position's duration (``ssnt_duration_posterior``, with
+``ssnt_duration_class_targets`` as the bridge to v2 classes), the counterparts of the first three on the v2
 duration-class lattice (``v2_fwd_bwd``, ``v2_viterbi_align``, ``v2_sample_align``), the exact N
 best duration paths on it (``v2_nbest_align``), the expected cost of a duration path on it
 (``v2_expected_cost``, ``V2ExpectedCost``, ``v2_duration_entropy``) and a fused multi-step decode
@@ -35,7 +37,7 @@ __all__ = [
     "levenshtein_edit_distance", "ssnt_fwd_bwd", "ssnt_viterbi_align", "ssnt_sample_align",
     "ssnt_nbest_align", "SSNTLatticeLoss",
     "ssnt_expected_cost", "SSNTExpectedCost", "ssnt_expected_cost_loss", "ssnt_alignment_entropy",
-    "ssnt_lattice_loss",
+    "ssnt_lattice_loss", "ssnt_duration_posterior", "ssnt_duration_class_targets",
     "lattice_beam_search_decode", "v2_lattice_beam_search_decode",
     "tone_latent_lattice_beam_search_decode", "v2_fwd_bwd", "v2_viterbi_align", "v2_sample_align",
     "v2_nbest_align", "V2DurationLoss",
@@ -595,6 +597,62 @@ def ssnt_expected_cost(log_trans, cost, step_len, pos_len, log_obs=None, *, term
         if go is not None:
             res["grad_obs"] = go
     return res
+
+
+def ssnt_duration_posterior(log_trans, step_len, pos_len, num_bins, log_obs=None, *,
+                            terminal_emit=True, out=None, check=True):
+    """The posterior distribution of every position's duration on the emit/shift lattice
+    (DESIGN.md 2.10).
+
+    Inputs as ``ssnt_fwd_bwd``; ``num_bins`` = D in [2, 256]. Returns a dict with ``dur_post``
+    (B,U,D) f32, whose bin index is the duration: ``dur_post[b,p,d]`` = P(position p lasts exactly d
+    steps) for d < D-1 (bin 0 is an exact 0) and ``dur_post[b,p,D-1]`` = P(it lasts at least D-1
+    steps); ``loss`` (B,) = -ln Z with the bits of ``ssnt_expected_cost``'s; and ``status``. A row
+    p < P_b sums to 1, rows p >= P_b are 0, and an infeasible utterance gets ``dur_post`` 0 and loss
+    +inf. ``out`` may pass preallocated tensors under the same keys."""
+    lib = load(require_gpu=True)
+    lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit)
+    dev = lt.device
+    B, T, U, _ = lt.shape
+    D = int(num_bins)
+    if not 2 <= D <= 256:
+        raise ValueError("num_bins must be in [2, 256]")
+    out = dict(out or {})
+    f32 = {"dtype": torch.float32, "name": "float32"}
+    dp = _buf(out, dev, "dur_post", (B, U, D), **f32)
+    loss = _buf(out, dev, "loss", (B,), **f32)
+    wsb = int(lib.ssnt_duration_posterior_workspace_size(B, T, U, D))
+    ws = _workspace(dev, wsb)
+    st = out.get("status")
+    if st is None:
+        st = _status(dev)
+    else:
+        st.zero_()
+    rc = lib.ssnt_duration_posterior_device(_p(lt), _p(lo), _p(sl), _p(pl), B, T, U, D, flags,
+                                            _p(dp), _p(loss), _p(ws), wsb, _p(st), _stream(dev))
+    _finish("ssnt_duration_posterior", rc, st, check)
+    return {"dur_post": dp, "loss": loss, "status": st}
+
+
+def ssnt_duration_class_targets(dur_post, duration_table):
+    """Soft targets over a v2 ``duration_table`` from ``dur_post`` (B,U,D) of
+    ``ssnt_duration_posterior``: pure torch, on any device. Returns ``(targets (B,U,C),
+    residual (B,U))``: ``targets[..., i] = dur_post[..., duration_table[i]]`` for a table value
+    below D-1, and 0 for a value >= D-1 (the tail bin is no exact duration); ``residual`` = the row
+    sum of ``dur_post`` minus the row sum of ``targets``, the posterior mass no class represents.
+    A table value that occurs twice raises ``ValueError`` (its mass would count twice)."""
+    if not isinstance(dur_post, torch.Tensor) or dur_post.dim() != 3:
+        raise ValueError("dur_post must be a (B,U,D) tensor")
+    table = torch.as_tensor(duration_table, dtype=torch.int64).reshape(-1).cpu()
+    if table.numel() and int(table.min()) < 0:
+        raise ValueError("duration_table must be >= 0")
+    if torch.unique(table).numel() != table.numel():
+        raise ValueError("duration_table holds a value twice")
+    D = dur_post.shape[-1]
+    exact = (table < D - 1).to(dur_post.device)
+    index = table.clamp(max=D - 1).to(dur_post.device)
+    targets = dur_post.index_select(-1, index) * exact.to(dur_post.dtype)
+    return targets, dur_post.sum(-1) - targets.sum(-1)
 
 
 class SSNTExpectedCost(torch.autograd.Function):

@@ -60,6 +60,9 @@ SIGNATURES = {
     "ssnt_expected_cost_workspace_size": (c_size_t, [c_int, c_int, c_int]),
     "ssnt_expected_cost_device": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P,
                                           P, c_size_t, P, P]),
+    "ssnt_duration_posterior_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ssnt_duration_posterior_device": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P,
+                                               P, c_size_t, P, P]),
     "ssnt_v2_fwd_bwd_workspace_size": (c_size_t, [c_int, c_int, c_int, c_bool]),
     "ssnt_v2_fwd_bwd_device": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_bool,
                                        c_bool, c_int, P, P, P, P, P, c_size_t, P, P]),
@@ -105,6 +108,9 @@ AB_SIGNATURES = {
     "ssnt_v2_sample_align_form": (c_int, [c_int, c_int]),
     "ssnt_expected_cost_chunk_rows": (c_int, [c_int, c_int]),
     "ssnt_expected_cost_launches": (c_int, [c_int]),
+    "ssnt_duration_posterior_block": (c_int, [c_int, c_int, c_int]),
+    "ssnt_duration_posterior_sweep_rows": (c_int, [c_int, c_int]),
+    "ssnt_duration_posterior_launches": (c_int, [c_int]),
     "ssnt_v2_expected_cost_chunk_steps": (c_int, [c_int]),
     "ssnt_v2_expected_cost_launches": (c_int, [c_int]),
     "ssnt_set_host_staging": (c_int, [c_int]),
@@ -181,6 +187,7 @@ class use_ab:
             ab.ssnt_fwd_bwd_wide_lag(0)
             ab.ssnt_v2_sample_align_form(0, 3)
             ab.ssnt_expected_cost_launches(3)
+            ab.ssnt_duration_posterior_launches(3)
             ab.ssnt_v2_expected_cost_launches(3)
             ab.ssnt_set_host_staging(1)
             ab.ssnt_set_host_sync(2)
