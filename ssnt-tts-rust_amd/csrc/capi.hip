@@ -390,17 +390,45 @@ __global__ void k_null() {}
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// what every *Args of the emit/shift lattice has, by name; an entry then sets its own fields
+template <typename Args>
+Args lattice_args(const float* log_trans, const float* log_obs, const int* step_len,
+                  const int* pos_len, int batch, int max_steps, int max_pos, int flags,
+                  void* workspace, size_t workspace_bytes, int* status) {
+  Args a{};
+  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
+  a.B = batch; a.T = max_steps; a.U = max_pos; a.flags = flags;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  return a;
+}
+
 // the launch arguments of a forward-backward call (the loss sum and raw-state fields stay null)
 FwdBwdArgs fwd_bwd_args(const float* log_trans, const float* log_obs, const int* step_len,
                         const int* pos_len, int batch, int max_steps, int max_pos, int flags,
                         float* loss, float* grad_trans, float* grad_obs, float* log_alpha,
                         float* log_beta, void* workspace, size_t workspace_bytes, int* status) {
-  FwdBwdArgs a{};
-  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
-  a.B = batch; a.T = max_steps; a.U = max_pos; a.flags = flags;
+  FwdBwdArgs a = lattice_args<FwdBwdArgs>(log_trans, log_obs, step_len, pos_len, batch, max_steps,
+                                          max_pos, flags, workspace, workspace_bytes, status);
   a.loss = loss; a.grad = grad_trans; a.grad_obs = grad_obs;
   a.log_alpha = log_alpha; a.log_beta = log_beta;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  return a;
+}
+
+// the max_total a v2 entry accepts (its query answers 0 for another, the entry INVALID_ARG)
+constexpr bool v2_max_total_ok(int max_total) { return max_total >= 0 && max_total <= (1 << 24); }
+
+// what every *Args of the v2 duration-class lattice has, by name
+template <typename Args>
+Args v2_args(const float* logits, const int* duration_table, const int* input_length,
+             const int* output_length, int batch, int max_steps, int duration_class_size,
+             int max_total, int zero_duration_id, bool allow_skip, bool test_mode, void* workspace,
+             size_t workspace_bytes, int* status) {
+  Args a{};
+  a.logits = logits; a.table = duration_table; a.input_length = input_length;
+  a.output_length = output_length; a.B = batch; a.Imax = max_steps; a.D = duration_class_size;
+  a.X = max_total + 1; a.zid = zero_duration_id; a.allow_skip = allow_skip;
+  a.test_mode = test_mode; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  a.status = status;
   return a;
 }
 
@@ -820,11 +848,9 @@ int ssnt_viterbi_align_device(const float* log_trans, const float* log_obs, cons
                               const int* pos_len, int batch, int max_steps, int max_pos, int flags,
                               float* log_prob, int* position, int* duration, void* workspace,
                               size_t workspace_bytes, int* status, void* stream) {
-  ViterbiArgs a{};
-  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
-  a.B = batch; a.T = max_steps; a.U = max_pos; a.flags = flags;
+  auto a = lattice_args<ViterbiArgs>(log_trans, log_obs, step_len, pos_len, batch, max_steps, max_pos,
+                                     flags, workspace, workspace_bytes, status);
   a.log_prob = log_prob; a.position = position; a.duration = duration;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
   return launch_viterbi(a, as_stream(stream));
 }
 
@@ -838,11 +864,9 @@ int ssnt_nbest_align_device(const float* log_trans, const float* log_obs, const 
                             int num_best, int flags, float* log_prob, int* position,
                             int* duration, void* workspace, size_t workspace_bytes, int* status,
                             void* stream) {
-  NbestAlignArgs a{};
-  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
-  a.B = batch; a.T = max_steps; a.U = max_pos; a.N = num_best; a.flags = flags;
-  a.log_prob = log_prob; a.position = position; a.duration = duration;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  auto a = lattice_args<NbestAlignArgs>(log_trans, log_obs, step_len, pos_len, batch, max_steps,
+                                        max_pos, flags, workspace, workspace_bytes, status);
+  a.N = num_best; a.log_prob = log_prob; a.position = position; a.duration = duration;
   return launch_nbest_align(a, as_stream(stream));
 }
 
@@ -857,11 +881,10 @@ int ssnt_sample_align_device(const float* log_trans, const float* log_obs, const
                              int max_pos, int num_samples, int flags, float* log_prob,
                              int* position, int* duration, void* workspace,
                              size_t workspace_bytes, int* status, void* stream) {
-  SampleAlignArgs a{};
-  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
-  a.uniform = uniform; a.B = batch; a.T = max_steps; a.U = max_pos; a.NS = num_samples;
-  a.flags = flags; a.log_prob = log_prob; a.position = position; a.duration = duration;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  auto a = lattice_args<SampleAlignArgs>(log_trans, log_obs, step_len, pos_len, batch, max_steps,
+                                         max_pos, flags, workspace, workspace_bytes, status);
+  a.uniform = uniform; a.NS = num_samples;
+  a.log_prob = log_prob; a.position = position; a.duration = duration;
   return launch_sample_align(a, as_stream(stream));
 }
 
@@ -875,12 +898,10 @@ int ssnt_expected_cost_device(const float* log_trans, const float* log_obs, cons
                               int max_pos, int flags, float* risk, float* loss, float* grad_trans,
                               float* grad_cost, float* grad_obs, void* workspace,
                               size_t workspace_bytes, int* status, void* stream) {
-  ExpectedCostArgs a{};
-  a.log_trans = log_trans; a.log_obs = log_obs; a.cost = cost; a.step_len = step_len;
-  a.pos_len = pos_len; a.B = batch; a.T = max_steps; a.U = max_pos; a.flags = flags;
-  a.risk = risk; a.loss = loss; a.grad_trans = grad_trans; a.grad_cost = grad_cost;
-  a.grad_obs = grad_obs; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
-  a.status = status;
+  auto a = lattice_args<ExpectedCostArgs>(log_trans, log_obs, step_len, pos_len, batch, max_steps,
+                                          max_pos, flags, workspace, workspace_bytes, status);
+  a.cost = cost; a.risk = risk; a.loss = loss;
+  a.grad_trans = grad_trans; a.grad_cost = grad_cost; a.grad_obs = grad_obs;
   return launch_expected_cost(a, as_stream(stream));
 }
 
@@ -894,11 +915,9 @@ int ssnt_duration_posterior_device(const float* log_trans, const float* log_obs,
                                    int num_bins, int flags, float* dur_post, float* loss,
                                    void* workspace, size_t workspace_bytes, int* status,
                                    void* stream) {
-  DurationPosteriorArgs a{};
-  a.log_trans = log_trans; a.log_obs = log_obs; a.step_len = step_len; a.pos_len = pos_len;
-  a.B = batch; a.T = max_steps; a.U = max_pos; a.D = num_bins; a.flags = flags;
-  a.dur_post = dur_post; a.loss = loss; a.workspace = workspace;
-  a.workspace_bytes = workspace_bytes; a.status = status;
+  auto a = lattice_args<DurationPosteriorArgs>(log_trans, log_obs, step_len, pos_len, batch, max_steps,
+                                               max_pos, flags, workspace, workspace_bytes, status);
+  a.D = num_bins; a.dur_post = dur_post; a.loss = loss;
   return launch_duration_posterior(a, as_stream(stream));
 }
 
@@ -912,20 +931,17 @@ int ssnt_v2_fwd_bwd_device(const float* logits, const int* duration_table, const
                            bool allow_skip, bool test_mode, int flags, float* loss, float* grad,
                            float* log_alpha, float* log_beta, void* workspace,
                            size_t workspace_bytes, int* status, void* stream) {
-  if (max_total < 0 || max_total > (1 << 24)) return SSNT_ERR_INVALID_ARG;
-  V2FwdBwdArgs a{};
-  a.logits = logits; a.table = duration_table; a.input_length = input_length;
-  a.output_length = output_length; a.B = batch; a.Imax = max_steps; a.D = duration_class_size;
-  a.X = max_total + 1; a.zid = zero_duration_id; a.allow_skip = allow_skip;
-  a.test_mode = test_mode; a.flags = flags; a.loss = loss; a.grad = grad;
-  a.log_alpha = log_alpha; a.log_beta = log_beta; a.workspace = workspace;
-  a.workspace_bytes = workspace_bytes; a.status = status;
+  if (!v2_max_total_ok(max_total)) return SSNT_ERR_INVALID_ARG;
+  auto a = v2_args<V2FwdBwdArgs>(logits, duration_table, input_length, output_length, batch, max_steps,
+                                 duration_class_size, max_total, zero_duration_id, allow_skip,
+                                 test_mode, workspace, workspace_bytes, status);
+  a.flags = flags; a.loss = loss; a.grad = grad; a.log_alpha = log_alpha; a.log_beta = log_beta;
   return launch_v2_fwd_bwd(a, as_stream(stream));
 }
 
 size_t ssnt_v2_expected_cost_workspace_size(int batch, int max_steps, int max_total,
                                             bool test_mode, bool need_grad) {
-  if (max_total < 0 || max_total > (1 << 24)) return 0;
+  if (!v2_max_total_ok(max_total)) return 0;
   return v2_expected_cost_workspace_bytes(batch, max_steps, max_total, test_mode, need_grad);
 }
 
@@ -935,19 +951,16 @@ int ssnt_v2_expected_cost_device(const float* logits, const float* cost, const i
                                  int zero_duration_id, bool allow_skip, bool test_mode,
                                  float* risk, float* loss, float* grad_logits, float* grad_cost,
                                  void* workspace, size_t workspace_bytes, int* status, void* stream) {
-  if (max_total < 0 || max_total > (1 << 24)) return SSNT_ERR_INVALID_ARG;
-  V2ExpectedCostArgs a{};
-  a.logits = logits; a.cost = cost; a.table = duration_table; a.input_length = input_length;
-  a.output_length = output_length; a.B = batch; a.Imax = max_steps; a.D = duration_class_size;
-  a.X = max_total + 1; a.zid = zero_duration_id; a.allow_skip = allow_skip;
-  a.test_mode = test_mode; a.risk = risk; a.loss = loss; a.grad_logits = grad_logits;
-  a.grad_cost = grad_cost; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
-  a.status = status;
+  if (!v2_max_total_ok(max_total)) return SSNT_ERR_INVALID_ARG;
+  auto a = v2_args<V2ExpectedCostArgs>(logits, duration_table, input_length, output_length, batch,
+                                       max_steps, duration_class_size, max_total, zero_duration_id,
+                                       allow_skip, test_mode, workspace, workspace_bytes, status);
+  a.cost = cost; a.risk = risk; a.loss = loss; a.grad_logits = grad_logits; a.grad_cost = grad_cost;
   return launch_v2_expected_cost(a, as_stream(stream));
 }
 
 size_t ssnt_v2_viterbi_align_workspace_size(int batch, int max_steps, int max_total, bool test_mode) {
-  if (max_total < 0 || max_total > (1 << 24)) return 0;
+  if (!v2_max_total_ok(max_total)) return 0;
   return v2_viterbi_workspace_bytes(batch, max_steps, max_total, test_mode);
 }
 
@@ -958,20 +971,17 @@ int ssnt_v2_viterbi_align_device(const float* logits, const int* duration_table,
                                  float* log_prob, int* duration_class, int* duration, int* total,
                                  void* workspace, size_t workspace_bytes, int* status,
                                  void* stream) {
-  if (max_total < 0 || max_total > (1 << 24)) return SSNT_ERR_INVALID_ARG;
-  V2ViterbiArgs a{};
-  a.logits = logits; a.table = duration_table; a.input_length = input_length;
-  a.output_length = output_length; a.B = batch; a.Imax = max_steps; a.D = duration_class_size;
-  a.X = max_total + 1; a.zid = zero_duration_id; a.allow_skip = allow_skip;
-  a.test_mode = test_mode; a.log_prob = log_prob; a.duration_class = duration_class;
-  a.duration = duration; a.total = total; a.workspace = workspace;
-  a.workspace_bytes = workspace_bytes; a.status = status;
+  if (!v2_max_total_ok(max_total)) return SSNT_ERR_INVALID_ARG;
+  auto a = v2_args<V2ViterbiArgs>(logits, duration_table, input_length, output_length, batch, max_steps,
+                                  duration_class_size, max_total, zero_duration_id, allow_skip,
+                                  test_mode, workspace, workspace_bytes, status);
+  a.log_prob = log_prob; a.duration_class = duration_class; a.duration = duration; a.total = total;
   return launch_v2_viterbi(a, as_stream(stream));
 }
 
 size_t ssnt_v2_nbest_align_workspace_size(int batch, int max_steps, int max_total, bool test_mode,
                                           int num_best) {
-  if (max_total < 0 || max_total > (1 << 24)) return 0;
+  if (!v2_max_total_ok(max_total)) return 0;
   return v2_nbest_workspace_bytes(batch, max_steps, max_total, test_mode, num_best);
 }
 
@@ -981,20 +991,18 @@ int ssnt_v2_nbest_align_device(const float* logits, const int* duration_table,
                                int zero_duration_id, bool allow_skip, bool test_mode, int num_best,
                                float* log_prob, int* duration_class, int* duration, int* total,
                                void* workspace, size_t workspace_bytes, int* status, void* stream) {
-  if (max_total < 0 || max_total > (1 << 24)) return SSNT_ERR_INVALID_ARG;
-  V2NbestArgs a{};
-  a.logits = logits; a.table = duration_table; a.input_length = input_length;
-  a.output_length = output_length; a.B = batch; a.Imax = max_steps; a.D = duration_class_size;
-  a.X = max_total + 1; a.N = num_best; a.zid = zero_duration_id; a.allow_skip = allow_skip;
-  a.test_mode = test_mode; a.log_prob = log_prob; a.duration_class = duration_class;
-  a.duration = duration; a.total = total; a.workspace = workspace;
-  a.workspace_bytes = workspace_bytes; a.status = status;
+  if (!v2_max_total_ok(max_total)) return SSNT_ERR_INVALID_ARG;
+  auto a = v2_args<V2NbestArgs>(logits, duration_table, input_length, output_length, batch, max_steps,
+                                duration_class_size, max_total, zero_duration_id, allow_skip,
+                                test_mode, workspace, workspace_bytes, status);
+  a.N = num_best;
+  a.log_prob = log_prob; a.duration_class = duration_class; a.duration = duration; a.total = total;
   return launch_v2_nbest_align(a, as_stream(stream));
 }
 
 size_t ssnt_v2_sample_align_workspace_size(int batch, int max_steps, int max_total, bool test_mode,
                                            int num_samples) {
-  if (max_total < 0 || max_total > (1 << 24) || num_samples < 1 || num_samples > 64) return 0;
+  if (!v2_max_total_ok(max_total) || num_samples < 1 || num_samples > 64) return 0;
   return v2_sample_workspace_bytes(batch, max_steps, max_total, test_mode);
 }
 
@@ -1005,14 +1013,12 @@ int ssnt_v2_sample_align_device(const float* logits, const int* duration_table,
                                 bool allow_skip, bool test_mode, int num_samples, float* log_prob,
                                 int* duration_class, int* duration, int* total, void* workspace,
                                 size_t workspace_bytes, int* status, void* stream) {
-  if (max_total < 0 || max_total > (1 << 24)) return SSNT_ERR_INVALID_ARG;
-  V2SampleArgs a{};
-  a.logits = logits; a.table = duration_table; a.input_length = input_length;
-  a.output_length = output_length; a.uniform = uniform; a.B = batch; a.Imax = max_steps;
-  a.D = duration_class_size; a.X = max_total + 1; a.NS = num_samples; a.zid = zero_duration_id;
-  a.allow_skip = allow_skip; a.test_mode = test_mode; a.log_prob = log_prob;
-  a.duration_class = duration_class; a.duration = duration; a.total = total;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  if (!v2_max_total_ok(max_total)) return SSNT_ERR_INVALID_ARG;
+  auto a = v2_args<V2SampleArgs>(logits, duration_table, input_length, output_length, batch, max_steps,
+                                 duration_class_size, max_total, zero_duration_id, allow_skip,
+                                 test_mode, workspace, workspace_bytes, status);
+  a.uniform = uniform; a.NS = num_samples;
+  a.log_prob = log_prob; a.duration_class = duration_class; a.duration = duration; a.total = total;
   return launch_v2_sample_align(a, as_stream(stream));
 }
 

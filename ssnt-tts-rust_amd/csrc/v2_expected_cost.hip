@@ -113,13 +113,8 @@ int set_v2_expected_cost_launches(int mask) {
 #endif
 
 int launch_v2_expected_cost(const V2ExpectedCostArgs& in, hipStream_t st) {
-  V2FwdBwdArgs a{};
-  a.logits = in.logits; a.table = in.table; a.input_length = in.input_length;
-  a.output_length = in.output_length; a.B = in.B; a.Imax = in.Imax; a.D = in.D; a.X = in.X;
-  a.zid = in.zid; a.allow_skip = in.allow_skip; a.test_mode = in.test_mode; a.flags = 0;
-  a.loss = in.loss; a.grad = in.grad_cost; a.workspace = in.workspace;
-  a.workspace_bytes = in.workspace_bytes; a.status = in.status;
-  a.fwd_only = false;
+  V2FwdBwdArgs a = v2_fwd_bwd_args_of(in);
+  a.loss = in.loss; a.grad = in.grad_cost;
   if (!in.cost || !in.risk) return SSNT_ERR_INVALID_ARG;
   size_t lds = 0, glds = 0;
   const int rc = f4_plan(a, false, lds, glds, true);

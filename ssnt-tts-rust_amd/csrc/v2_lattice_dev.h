@@ -17,6 +17,7 @@
 #include <stddef.h>
 
 #include "buffer_ops.h"
+#include "launch_util.h"
 #include "ssnt_internal.h"
 #include "ssnt_tts_c.h"
 #include "xf_math.h"
@@ -108,6 +109,45 @@ inline size_t v2_fwd_bwd_wcap(int max_total, bool test_mode) {
   if (test_mode) return (size_t)X;
   const size_t band = (size_t)(0.15 * (double)max_total) + 8;
   return band < (size_t)X ? band : (size_t)X;
+}
+
+// ---- host: what the v2 launchers share (as aln_check_args / aln_workspace_ok in align_dev.h) ----
+// the class-count instantiation DC that D classes run on
+inline int v2_class_cap(int D) { return D <= 8 ? 8 : D <= 16 ? 16 : D <= 32 ? 32 : 64; }
+
+// what the best-path entries (v2_viterbi.hip, v2_nbest_align.hip) refuse alike, in this order, and
+// Wcap set; SSNT_OK with B == 0: nothing to launch. `own_ok`: the entry's own scalar arguments
+template <typename Args>
+inline int v2_check_args(Args& a, bool own_ok = true) {
+  if (a.B < 0 || !own_ok) return SSNT_ERR_INVALID_ARG;
+  if (a.B == 0) return SSNT_OK;
+  if (a.Imax <= 0 || a.D <= 0 || a.X <= 0) return SSNT_ERR_INVALID_ARG;
+  if (!a.logits || !a.table || !a.input_length || !a.output_length || !a.log_prob) return SSNT_ERR_INVALID_ARG;
+  if (a.D > 64) return SSNT_ERR_UNSUPPORTED;  // unrolled over <= 64 classes; a class is 6 bits
+  a.Wcap = (int)v2_fwd_bwd_wcap(a.X - 1, a.test_mode);
+  return SSNT_OK;
+}
+// one utterance's backpointers (`bp_bytes`) and its class log-probs are addressed with 32-bit offsets
+template <typename Args>
+inline bool v2_offsets_ok(const Args& a, size_t bp_bytes) {
+  return bp_bytes <= 0x7fffffffu - 64 && (size_t)a.Imax * a.D * sizeof(float) <= 0x7fffffffu;
+}
+// the workspace a shape needs whose backpointers do not fit LDS: given, large enough, aligned
+template <typename Args>
+inline bool v2_workspace_ok(const Args& a, size_t need, size_t align) {
+  return a.workspace && a.workspace_bytes >= need && aligned_to(a.workspace, align);
+}
+
+// F4's arguments of a call on the same problem: the fields every v2 *Args has, by name (the
+// outputs and what the launcher sets stay zero)
+template <typename Args>
+inline V2FwdBwdArgs v2_fwd_bwd_args_of(const Args& in) {
+  V2FwdBwdArgs a{};
+  a.logits = in.logits; a.table = in.table; a.input_length = in.input_length;
+  a.output_length = in.output_length; a.B = in.B; a.Imax = in.Imax; a.D = in.D; a.X = in.X;
+  a.zid = in.zid; a.allow_skip = in.allow_skip; a.test_mode = in.test_mode;
+  a.workspace = in.workspace; a.workspace_bytes = in.workspace_bytes; a.status = in.status;
+  return a;
 }
 
 // ---- F4's device code (v2_fwd_bwd.hip, v2_expected_cost.hip) ----

@@ -581,27 +581,19 @@ size_t v2_nbest_workspace_bytes(int B, int Imax, int max_total, bool test_mode, 
 
 int launch_v2_nbest_align(const V2NbestArgs& in, hipStream_t st) {
   V2NbestArgs a = in;
-  if (a.B < 0 || a.N < 1 || a.N > kVnMaxBest) return SSNT_ERR_INVALID_ARG;
-  if (a.B == 0) return SSNT_OK;
-  if (a.Imax <= 0 || a.D <= 0 || a.X <= 0) return SSNT_ERR_INVALID_ARG;
-  if (!a.logits || !a.table || !a.input_length || !a.output_length || !a.log_prob) return SSNT_ERR_INVALID_ARG;
-  if (a.D > 64) return SSNT_ERR_UNSUPPORTED;  // a class is 6 bits of a backpointer entry
-  a.Wcap = (int)v2_fwd_bwd_wcap(a.X - 1, a.test_mode);
+  const int rc = v2_check_args(a, a.N >= 1 && a.N <= kVnMaxBest);
+  if (rc != SSNT_OK || a.B == 0) return rc;
   const int NB = vn_round(a.N);
-  // (one utterance's backpointer entries, its outputs and its class log-probs are addressed with
-  // 32-bit offsets)
-  if ((size_t)a.Imax * vn_row_bytes_q(a.Wcap, NB) > 0x7fffffffu - 64) return SSNT_ERR_UNSUPPORTED;
-  if ((size_t)a.Imax * a.D * sizeof(float) > 0x7fffffffu) return SSNT_ERR_UNSUPPORTED;
+  // (backpointer entries; one utterance's outputs are no larger)
+  if (!v2_offsets_ok(a, (size_t)a.Imax * vn_row_bytes_q(a.Wcap, NB))) return SSNT_ERR_UNSUPPORTED;
   const bool path = a.duration_class || a.duration;
   const bool fit = vn_bits_fit(a.Imax, a.Wcap, NB);
   const int mode = !path ? 0 : fit ? 1 : 2;
-  const int DC = a.D <= 8 ? 8 : a.D <= 16 ? 16 : a.D <= 32 ? 32 : 64;
+  const int DC = v2_class_cap(a.D);
   // rows that do not fit LDS at this list width: unsupported, whatever the workspace
   if (vn_layout(a.Imax, a.Wcap, DC, NB, mode).total > kVnLdsBudget) return SSNT_ERR_UNSUPPORTED;
-  if (mode == 2) {
-    const size_t need = v2_nbest_workspace_bytes(a.B, a.Imax, a.X - 1, a.test_mode, a.N);
-    if (!a.workspace || a.workspace_bytes < need || !aligned_to(a.workspace, 4)) return SSNT_ERR_WORKSPACE;
-  }
+  if (mode == 2 && !v2_workspace_ok(a, v2_nbest_workspace_bytes(a.B, a.Imax, a.X - 1, a.test_mode, a.N), 4))
+    return SSNT_ERR_WORKSPACE;
   if (DC == 8) return launch_vn_nb<8>(a, NB, mode, st);
   if (DC == 16) return launch_vn_nb<16>(a, NB, mode, st);
   if (DC == 32) return launch_vn_nb<32>(a, NB, mode, st);

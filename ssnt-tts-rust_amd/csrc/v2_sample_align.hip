@@ -376,11 +376,7 @@ int launch_v2_sample_align(const V2SampleArgs& in, hipStream_t st) {
   if (a.B == 0) return SSNT_OK;
   if (!a.uniform || !a.log_prob) return SSNT_ERR_INVALID_ARG;
   // the forward launch's arguments; its refusals (F4's, in F4's order) before anything is launched
-  V2FwdBwdArgs f{};
-  f.logits = a.logits; f.table = a.table; f.input_length = a.input_length; f.output_length = a.output_length;
-  f.B = a.B; f.Imax = a.Imax; f.D = a.D; f.X = a.X; f.zid = a.zid; f.allow_skip = a.allow_skip;
-  f.test_mode = a.test_mode; f.workspace = a.workspace; f.workspace_bytes = a.workspace_bytes;
-  f.status = a.status;
+  V2FwdBwdArgs f = v2_fwd_bwd_args_of(a);
   if (a.workspace && !aligned_to(a.workspace, sizeof(xf))) {
     f.workspace = nullptr;  // (refused as a missing one, after F4's other checks)
   }

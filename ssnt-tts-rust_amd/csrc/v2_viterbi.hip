@@ -433,25 +433,17 @@ size_t v2_viterbi_workspace_bytes(int B, int Imax, int max_total, bool test_mode
 
 int launch_v2_viterbi(const V2ViterbiArgs& in, hipStream_t st) {
   V2ViterbiArgs a = in;
-  if (a.B < 0) return SSNT_ERR_INVALID_ARG;
-  if (a.B == 0) return SSNT_OK;
-  if (a.Imax <= 0 || a.D <= 0 || a.X <= 0) return SSNT_ERR_INVALID_ARG;
-  if (!a.logits || !a.table || !a.input_length || !a.output_length || !a.log_prob) return SSNT_ERR_INVALID_ARG;
-  if (a.D > 64) return SSNT_ERR_UNSUPPORTED;  // candidates unrolled over <= 64 classes; class bytes
-  a.Wcap = (int)v2_fwd_bwd_wcap(a.X - 1, a.test_mode);
-  // (backpointer bytes of one utterance and its class log-probs are addressed with 32-bit offsets)
-  if ((size_t)a.Imax * a.Wcap > 0x7fffffffu - 64) return SSNT_ERR_UNSUPPORTED;
-  if ((size_t)a.Imax * a.D * sizeof(float) > 0x7fffffffu) return SSNT_ERR_UNSUPPORTED;
+  const int rc = v2_check_args(a);
+  if (rc != SSNT_OK || a.B == 0) return rc;
+  if (!v2_offsets_ok(a, (size_t)a.Imax * a.Wcap)) return SSNT_ERR_UNSUPPORTED;  // (backpointer bytes)
   const bool path = a.duration_class || a.duration;
   const bool fit = v2v_bits_fit(a.Imax, a.Wcap);
   const int mode = !path ? 0 : fit ? 1 : 2;
-  const int DC = a.D <= 8 ? 8 : a.D <= 16 ? 16 : a.D <= 32 ? 32 : 64;
+  const int DC = v2_class_cap(a.D);
   // a row that does not fit LDS: unsupported, whatever the workspace
   if (v2v_layout(a.Imax, a.Wcap, DC, mode).total > kV2vLdsBudget) return SSNT_ERR_UNSUPPORTED;
-  if (mode == 2) {
-    const size_t need = v2_viterbi_workspace_bytes(a.B, a.Imax, a.X - 1, a.test_mode);
-    if (!a.workspace || a.workspace_bytes < need || !aligned_to(a.workspace, 4)) return SSNT_ERR_WORKSPACE;
-  }
+  if (mode == 2 && !v2_workspace_ok(a, v2_viterbi_workspace_bytes(a.B, a.Imax, a.X - 1, a.test_mode), 4))
+    return SSNT_ERR_WORKSPACE;
   if (DC == 8) return launch_v2v_mode<8>(a, mode, st);
   if (DC == 16) return launch_v2v_mode<16>(a, mode, st);
   if (DC == 32) return launch_v2v_mode<32>(a, mode, st);

@@ -282,6 +282,12 @@ def _sum_state(dev, B):
     return t
 
 
+def _shaped(t, dtype, name, shape):
+    """_dev, in `shape`: a new view only where that is not the tensor's shape already."""
+    t = _dev(t, dtype, name)
+    return t if t.shape == shape else t.reshape(shape)
+
+
 def _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit, zero_infinity=False):
     """The checked device tensors (lt, sl, pl, lo) of a call on the emit/shift lattice and its
     flags word."""
@@ -289,24 +295,87 @@ def _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit, zero_i
     B, T, U, two = lt.shape
     if two != 2:
         raise ValueError("log_trans must be (B,T,U,2)")
-    sl = _dev(step_len, torch.int32, "step_len").reshape(B)
-    pl = _dev(pos_len, torch.int32, "pos_len").reshape(B)
-    lo = None if log_obs is None else _dev(log_obs, torch.float32, "log_obs").reshape(B, T, U)
+    sl = _shaped(step_len, torch.int32, "step_len", (B,))
+    pl = _shaped(pos_len, torch.int32, "pos_len", (B,))
+    lo = None if log_obs is None else _shaped(log_obs, torch.float32, "log_obs", (B, T, U))
     flags = (FLAG_TERMINAL_EMIT if terminal_emit else 0) | (FLAG_ZERO_INFINITY if zero_infinity else 0)
     return lt, sl, pl, lo, flags
 
 
-def _buf(out, dev, key, shape, dtype, want=True, name=None):
-    """Output tensor `key`: the caller's out[key] when given (checked), else a new one; None
-    when not wanted. `name` is how the dtype reads in the error message."""
-    if not want:
-        return None
-    t = out.get(key)
-    if t is None:
-        t = torch.empty(shape, dtype=dtype, device=dev)
-    elif tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
-        raise ValueError(f"out[{key!r}] must be a contiguous {name or dtype} tensor of shape {shape}")
-    return t
+def _v2_inputs(logits, duration_table, input_length, output_length, max_total):
+    """The checked device tensors (lg, table, il, ol) of a call on the v2 duration-class lattice
+    and its max_total: the given one, else max(output_length), read back from the device."""
+    lg = _dev(logits, torch.float32, "logits")
+    B, _, D = lg.shape
+    table = _shaped(duration_table, torch.int32, "duration_table", (D,))
+    il = _shaped(input_length, torch.int32, "input_length", (B,))
+    ol = _shaped(output_length, torch.int32, "output_length", (B,))
+    if max_total is None:
+        max_total = int(ol.max().item()) if B > 0 else 0
+    return lg, table, il, ol, int(max_total)
+
+
+def _uniform(uniform, dev, shape, dims, generator):
+    """The randomness of a sampler: the caller's `uniform` (checked against `shape`, which reads
+    `dims` in the error message), else drawn on the device."""
+    if uniform is None:
+        return torch.rand(shape, device=dev, dtype=torch.float32, generator=generator)
+    un = _dev(uniform, torch.float32, "uniform")
+    if tuple(un.shape) != shape:
+        raise ValueError(f"uniform must be {dims} = {shape}")
+    return un
+
+
+def _a(t):
+    """An optional tensor as a pointer argument of a lattice call: its plain address (ctypes
+    converts it by the argtypes every symbol of _lib.SIGNATURES has), None as NULL."""
+    return None if t is None else t.data_ptr()
+
+
+class _Call:
+    """One call of a lattice entry point: the steps all of them share (DESIGN.md "Host call
+    protocol"). ``buf`` hands out the outputs and registers the wanted ones in ``res``, the dict
+    the public function returns; ``workspace`` queries and allocates; ``run`` takes or makes the
+    status word, calls the library and checks what it returned."""
+
+    ws, wsb = None, 0  # (no workspace unless workspace() makes one)
+
+    def __init__(self, where, dev, out, check):
+        self.where, self.dev, self.out, self.check, self.res = where, dev, dict(out or {}), check, {}
+
+    def buf(self, key, shape, dtype=torch.float32, want=True):
+        """Output `key`: the caller's out[key] when given (checked), else a new tensor, kept as
+        res[key]; returns its address. Not wanted: None (NULL to the library), absent from res."""
+        if not want:
+            return None
+        t = self.out.get(key)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=self.dev)
+        elif tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"out[{key!r}] must be a contiguous {str(dtype)[6:]} tensor of shape {shape}")
+        self.res[key] = t
+        return t.data_ptr()
+
+    def workspace(self, query, *shape):
+        """The workspace `query(*shape)` asks for. A call that needs none (no path, no gradient)
+        does not ask: the library then gets NULL and 0 bytes."""
+        self.wsb = int(query(*shape))
+        self.ws = _workspace(self.dev, self.wsb)
+
+    def run(self, fn, *args, tail=()):
+        """fn(*args, workspace, workspace_bytes, status, *tail, stream), args and tail as the
+        library takes them (addresses, integers). The status word is out["status"], zeroed, else a
+        new one. Returns ``res``."""
+        st = self.out.get("status")
+        if st is None:
+            st = _status(self.dev)
+        else:
+            st.zero_()
+        rc = fn(*args, _a(self.ws), self.wsb, st.data_ptr(), *tail, _stream(self.dev))
+        if rc != 0 or self.check:
+            _finish(self.where, rc, st, self.check)
+        self.res["status"] = st
+        return self.res
 
 
 def ssnt_fwd_bwd(log_trans, step_len, pos_len, log_obs=None, *, terminal_emit=True,
@@ -325,80 +394,29 @@ def ssnt_fwd_bwd(log_trans, step_len, pos_len, log_obs=None, *, terminal_emit=Tr
     ``log_beta`` as float64, formed on the GPU from the kernel's split-exponent state (the
     north_star's 1e-5 bar on log-alpha / log-beta is below an f32 ulp at BASELINE magnitudes).
     """
-    if debug64:
-        if out is not None or loss_sum or debug:
-            # (the debug64 entry has its own float64 outputs and no fused loss sum: the C entry
-            # rejects loss_sum with SSNT_ERR_INVALID_ARG, and out= / debug= would be ignored)
-            raise ValueError("debug64=True cannot be combined with out=, loss_sum=True or debug=True")
-        return _fwd_bwd_debug64(log_trans, step_len, pos_len, log_obs, terminal_emit,
-                                zero_infinity, need_grad, check)
+    if debug64 and (out is not None or loss_sum or debug):
+        # (the debug64 entry has its own float64 outputs and no fused loss sum: the C entry
+        # rejects loss_sum with SSNT_ERR_INVALID_ARG, and out= / debug= would be ignored)
+        raise ValueError("debug64=True cannot be combined with out=, loss_sum=True or debug=True")
     lib = load(require_gpu=True)
     lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit,
                                             zero_infinity)
-    dev = lt.device
     B, T, U, _ = lt.shape
-    out = dict(out or {})
-    f32 = {"dtype": torch.float32, "name": "float32"}
-    loss = _buf(out, dev, "loss", (B,), **f32)
-    grad = _buf(out, dev, "grad", (B, T, U, 2), want=need_grad, **f32)
-    gobs = _buf(out, dev, "grad_obs", (B, T, U), want=need_grad and lo is not None, **f32)
-    la = _buf(out, dev, "log_alpha", (B, T, U), want=debug, **f32)
-    lb = _buf(out, dev, "log_beta", (B, T, U), want=debug, **f32)
-    wsb = int(lib.ssnt_fwd_bwd_workspace_size(B, T, U))
-    ws = _workspace(dev, wsb)
-    st = out.get("status")
-    if st is None:
-        st = _status(dev)
-    else:
-        st.zero_()
+    name = "ssnt_fwd_bwd_debug64" if debug64 else "ssnt_fwd_bwd"
+    wide = torch.float64 if debug64 else torch.float32
+    c = _Call(name, lt.device, out, check)
+    loss = c.buf("loss", (B,), wide)
+    grad = c.buf("grad", (B, T, U, 2), want=need_grad)
+    gobs = c.buf("grad_obs", (B, T, U), want=need_grad and lo is not None)
+    la = c.buf("log_alpha", (B, T, U), wide, want=debug or debug64)
+    lb = c.buf("log_beta", (B, T, U), wide, want=debug or debug64)
+    c.workspace(getattr(lib, name + "_workspace_size"), B, T, U)
+    fn, tail = getattr(lib, name + "_device"), ()
     if loss_sum:
-        lsum = _buf(out, dev, "loss_sum", (1,), **f32)
-        rc = lib.ssnt_fwd_bwd_sum_device(_p(lt), _p(lo), _p(sl), _p(pl), B, T, U, flags, _p(loss),
-                                         _p(grad), _p(gobs), _p(la), _p(lb), _p(ws), wsb, _p(st),
-                                         _p(lsum), _p(_sum_state(dev, B)), _stream(dev))
-    else:
-        rc = lib.ssnt_fwd_bwd_device(_p(lt), _p(lo), _p(sl), _p(pl), B, T, U, flags, _p(loss),
-                                     _p(grad), _p(gobs), _p(la), _p(lb), _p(ws), wsb, _p(st),
-                                     _stream(dev))
-    _finish("ssnt_fwd_bwd", rc, st, check)
-    res = {"loss": loss, "status": st}
-    if loss_sum:
-        res["loss_sum"] = lsum
-    if grad is not None:
-        res["grad"] = grad
-    if gobs is not None:
-        res["grad_obs"] = gobs
-    if debug:
-        res["log_alpha"] = la
-        res["log_beta"] = lb
-    return res
-
-
-def _fwd_bwd_debug64(log_trans, step_len, pos_len, log_obs, terminal_emit, zero_infinity,
-                     need_grad, check):
-    lib = load(require_gpu=True)
-    lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit,
-                                            zero_infinity)
-    dev = lt.device
-    B, T, U, _ = lt.shape
-    loss = _buf({}, dev, "loss", (B,), torch.float64)
-    la = _buf({}, dev, "log_alpha", (B, T, U), torch.float64)
-    lb = _buf({}, dev, "log_beta", (B, T, U), torch.float64)
-    grad = _buf({}, dev, "grad", (B, T, U, 2), torch.float32, want=need_grad)
-    gobs = _buf({}, dev, "grad_obs", (B, T, U), torch.float32, want=need_grad and lo is not None)
-    wsb = int(lib.ssnt_fwd_bwd_debug64_workspace_size(B, T, U))
-    ws = _workspace(dev, wsb)
-    st = _status(dev)
-    rc = lib.ssnt_fwd_bwd_debug64_device(_p(lt), _p(lo), _p(sl), _p(pl), B, T, U, flags, _p(loss),
-                                         _p(grad), _p(gobs), _p(la), _p(lb), _p(ws), wsb, _p(st),
-                                         _stream(dev))
-    _finish("ssnt_fwd_bwd_debug64", rc, st, check)
-    res = {"loss": loss, "log_alpha": la, "log_beta": lb, "status": st}
-    if grad is not None:
-        res["grad"] = grad
-    if gobs is not None:
-        res["grad_obs"] = gobs
-    return res
+        fn = lib.ssnt_fwd_bwd_sum_device
+        tail = (c.buf("loss_sum", (1,)), _sum_state(lt.device, B).data_ptr())
+    return c.run(fn, lt.data_ptr(), _a(lo), sl.data_ptr(), pl.data_ptr(), B, T, U, flags,
+                 loss, grad, gobs, la, lb, tail=tail)
 
 
 def ssnt_viterbi_align(log_trans, step_len, pos_len, log_obs=None, *, terminal_emit=True,
@@ -413,27 +431,15 @@ def ssnt_viterbi_align(log_trans, step_len, pos_len, log_obs=None, *, terminal_e
     tensors under the same keys."""
     lib = load(require_gpu=True)
     lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit)
-    dev = lt.device
     B, T, U, _ = lt.shape
-    out = dict(out or {})
-    lp = _buf(out, dev, "log_prob", (B,), torch.float32)
-    pos = _buf(out, dev, "position", (B, T), torch.int32, want=need_path)
-    dur = _buf(out, dev, "duration", (B, U), torch.int32, want=need_path)
-    wsb = int(lib.ssnt_viterbi_align_workspace_size(B, T, U)) if need_path else 0
-    ws = _workspace(dev, wsb)
-    st = out.get("status")
-    if st is None:
-        st = _status(dev)
-    else:
-        st.zero_()
-    rc = lib.ssnt_viterbi_align_device(_p(lt), _p(lo), _p(sl), _p(pl), B, T, U, flags, _p(lp),
-                                       _p(pos), _p(dur), _p(ws), wsb, _p(st), _stream(dev))
-    _finish("ssnt_viterbi_align", rc, st, check)
-    res = {"log_prob": lp, "status": st}
+    c = _Call("ssnt_viterbi_align", lt.device, out, check)
+    lp = c.buf("log_prob", (B,))
+    pos = c.buf("position", (B, T), torch.int32, want=need_path)
+    dur = c.buf("duration", (B, U), torch.int32, want=need_path)
     if need_path:
-        res["position"] = pos
-        res["duration"] = dur
-    return res
+        c.workspace(lib.ssnt_viterbi_align_workspace_size, B, T, U)
+    return c.run(lib.ssnt_viterbi_align_device, lt.data_ptr(), _a(lo), sl.data_ptr(),
+                 pl.data_ptr(), B, T, U, flags, lp, pos, dur)
 
 
 def ssnt_nbest_align(log_trans, step_len, pos_len, num_best, log_obs=None, *, terminal_emit=True,
@@ -450,29 +456,19 @@ def ssnt_nbest_align(log_trans, step_len, pos_len, num_best, log_obs=None, *, te
     ``count`` only. ``out`` may pass preallocated tensors under the same keys (not ``count``)."""
     lib = load(require_gpu=True)
     lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit)
-    dev = lt.device
     B, T, U, _ = lt.shape
     N = int(num_best)
-    out = dict(out or {})
     shape_n = max(N, 0)  # (an N the library refuses: the call below reports it)
-    lp = _buf(out, dev, "log_prob", (B, shape_n), torch.float32)
-    pos = _buf(out, dev, "position", (B, shape_n, T), torch.int32, want=need_path)
-    dur = _buf(out, dev, "duration", (B, shape_n, U), torch.int32, want=need_path)
-    wsb = int(lib.ssnt_nbest_align_workspace_size(B, T, U, N)) if need_path else 0
-    ws = _workspace(dev, wsb)
-    st = out.get("status")
-    if st is None:
-        st = _status(dev)
-    else:
-        st.zero_()
-    rc = lib.ssnt_nbest_align_device(_p(lt), _p(lo), _p(sl), _p(pl), B, T, U, N, flags, _p(lp),
-                                     _p(pos), _p(dur), _p(ws), wsb, _p(st), _stream(dev))
-    _finish("ssnt_nbest_align", rc, st, check)
-    res = {"log_prob": lp, "count": (lp > float("-inf")).sum(dim=1).to(torch.int32), "status": st}
+    c = _Call("ssnt_nbest_align", lt.device, out, check)
+    lp = c.buf("log_prob", (B, shape_n))
+    pos = c.buf("position", (B, shape_n, T), torch.int32, want=need_path)
+    dur = c.buf("duration", (B, shape_n, U), torch.int32, want=need_path)
     if need_path:
-        res["position"] = pos
-        res["duration"] = dur
-    return res
+        c.workspace(lib.ssnt_nbest_align_workspace_size, B, T, U, N)
+    c.run(lib.ssnt_nbest_align_device, lt.data_ptr(), _a(lo), sl.data_ptr(), pl.data_ptr(),
+          B, T, U, N, flags, lp, pos, dur)
+    c.res["count"] = (c.res["log_prob"] > float("-inf")).sum(dim=1).to(torch.int32)
+    return c.res
 
 
 def ssnt_sample_align(log_trans, step_len, pos_len, num_samples, log_obs=None, *, uniform=None,
@@ -489,34 +485,16 @@ def ssnt_sample_align(log_trans, step_len, pos_len, num_samples, log_obs=None, *
     ``out`` may pass preallocated tensors under the same keys."""
     lib = load(require_gpu=True)
     lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit)
-    dev = lt.device
     B, T, U, _ = lt.shape
     K = int(num_samples)
-    if uniform is None:
-        un = torch.rand((B, K, T), device=dev, dtype=torch.float32, generator=generator)
-    else:
-        un = _dev(uniform, torch.float32, "uniform")
-        if tuple(un.shape) != (B, K, T):
-            raise ValueError(f"uniform must be (B,K,T) = {(B, K, T)}")
-    out = dict(out or {})
-    lp = _buf(out, dev, "log_prob", (B, K), torch.float32)
-    pos = _buf(out, dev, "position", (B, K, T), torch.int32, want=need_path)
-    dur = _buf(out, dev, "duration", (B, K, U), torch.int32, want=need_path)
-    wsb = int(lib.ssnt_sample_align_workspace_size(B, T, U, K))
-    ws = _workspace(dev, wsb)
-    st = out.get("status")
-    if st is None:
-        st = _status(dev)
-    else:
-        st.zero_()
-    rc = lib.ssnt_sample_align_device(_p(lt), _p(lo), _p(sl), _p(pl), _p(un), B, T, U, K, flags,
-                                      _p(lp), _p(pos), _p(dur), _p(ws), wsb, _p(st), _stream(dev))
-    _finish("ssnt_sample_align", rc, st, check)
-    res = {"log_prob": lp, "uniform": un, "status": st}
-    if need_path:
-        res["position"] = pos
-        res["duration"] = dur
-    return res
+    c = _Call("ssnt_sample_align", lt.device, out, check)
+    un = c.res["uniform"] = _uniform(uniform, lt.device, (B, K, T), "(B,K,T)", generator)
+    lp = c.buf("log_prob", (B, K))
+    pos = c.buf("position", (B, K, T), torch.int32, want=need_path)
+    dur = c.buf("duration", (B, K, U), torch.int32, want=need_path)
+    c.workspace(lib.ssnt_sample_align_workspace_size, B, T, U, K)
+    return c.run(lib.ssnt_sample_align_device, lt.data_ptr(), _a(lo), sl.data_ptr(),
+                 pl.data_ptr(), un.data_ptr(), B, T, U, K, flags, lp, pos, dur)
 
 
 class SSNTLatticeLoss(torch.autograd.Function):
@@ -567,36 +545,20 @@ def ssnt_expected_cost(log_trans, cost, step_len, pos_len, log_obs=None, *, term
     preallocated tensors under the same keys."""
     lib = load(require_gpu=True)
     lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit)
-    dev = lt.device
     B, T, U, _ = lt.shape
     cs = _dev(cost, torch.float32, "cost")
     if tuple(cs.shape) != (B, T, U, 2):
         raise ValueError(f"cost must be (B,T,U,2) = {(B, T, U, 2)}")
-    out = dict(out or {})
-    f32 = {"dtype": torch.float32, "name": "float32"}
-    risk = _buf(out, dev, "risk", (B,), **f32)
-    loss = _buf(out, dev, "loss", (B,), **f32)
-    gt = _buf(out, dev, "grad_trans", (B, T, U, 2), want=need_grad, **f32)
-    gc = _buf(out, dev, "grad_cost", (B, T, U, 2), want=need_grad, **f32)
-    go = _buf(out, dev, "grad_obs", (B, T, U), want=need_grad and lo is not None, **f32)
-    wsb = int(lib.ssnt_expected_cost_workspace_size(B, T, U)) if need_grad else 0
-    ws = _workspace(dev, wsb)
-    st = out.get("status")
-    if st is None:
-        st = _status(dev)
-    else:
-        st.zero_()
-    rc = lib.ssnt_expected_cost_device(_p(lt), _p(lo), _p(cs), _p(sl), _p(pl), B, T, U, flags,
-                                       _p(risk), _p(loss), _p(gt), _p(gc), _p(go), _p(ws), wsb,
-                                       _p(st), _stream(dev))
-    _finish("ssnt_expected_cost", rc, st, check)
-    res = {"risk": risk, "loss": loss, "status": st}
+    c = _Call("ssnt_expected_cost", lt.device, out, check)
+    risk = c.buf("risk", (B,))
+    loss = c.buf("loss", (B,))
+    gt = c.buf("grad_trans", (B, T, U, 2), want=need_grad)
+    gc = c.buf("grad_cost", (B, T, U, 2), want=need_grad)
+    go = c.buf("grad_obs", (B, T, U), want=need_grad and lo is not None)
     if need_grad:
-        res["grad_trans"] = gt
-        res["grad_cost"] = gc
-        if go is not None:
-            res["grad_obs"] = go
-    return res
+        c.workspace(lib.ssnt_expected_cost_workspace_size, B, T, U)
+    return c.run(lib.ssnt_expected_cost_device, lt.data_ptr(), _a(lo), cs.data_ptr(),
+                 sl.data_ptr(), pl.data_ptr(), B, T, U, flags, risk, loss, gt, gc, go)
 
 
 def ssnt_duration_posterior(log_trans, step_len, pos_len, num_bins, log_obs=None, *,
@@ -612,26 +574,16 @@ def ssnt_duration_posterior(log_trans, step_len, pos_len, num_bins, log_obs=None
     +inf. ``out`` may pass preallocated tensors under the same keys."""
     lib = load(require_gpu=True)
     lt, sl, pl, lo, flags = _lattice_inputs(log_trans, step_len, pos_len, log_obs, terminal_emit)
-    dev = lt.device
     B, T, U, _ = lt.shape
     D = int(num_bins)
     if not 2 <= D <= 256:
         raise ValueError("num_bins must be in [2, 256]")
-    out = dict(out or {})
-    f32 = {"dtype": torch.float32, "name": "float32"}
-    dp = _buf(out, dev, "dur_post", (B, U, D), **f32)
-    loss = _buf(out, dev, "loss", (B,), **f32)
-    wsb = int(lib.ssnt_duration_posterior_workspace_size(B, T, U, D))
-    ws = _workspace(dev, wsb)
-    st = out.get("status")
-    if st is None:
-        st = _status(dev)
-    else:
-        st.zero_()
-    rc = lib.ssnt_duration_posterior_device(_p(lt), _p(lo), _p(sl), _p(pl), B, T, U, D, flags,
-                                            _p(dp), _p(loss), _p(ws), wsb, _p(st), _stream(dev))
-    _finish("ssnt_duration_posterior", rc, st, check)
-    return {"dur_post": dp, "loss": loss, "status": st}
+    c = _Call("ssnt_duration_posterior", lt.device, out, check)
+    dp = c.buf("dur_post", (B, U, D))
+    loss = c.buf("loss", (B,))
+    c.workspace(lib.ssnt_duration_posterior_workspace_size, B, T, U, D)
+    return c.run(lib.ssnt_duration_posterior_device, lt.data_ptr(), _a(lo), sl.data_ptr(),
+                 pl.data_ptr(), B, T, U, D, flags, dp, loss)
 
 
 def ssnt_duration_class_targets(dur_post, duration_table):
@@ -731,40 +683,17 @@ def v2_fwd_bwd(logits, duration_table, input_length, output_length, zero_duratio
     ``log_alpha`` / ``log_beta`` (B,T+1,max_total+1). Rows of ``grad`` at steps >= I_b are 0.
     ``out`` may pass preallocated tensors under the same keys."""
     lib = load(require_gpu=True)
-    lg = _dev(logits, torch.float32, "logits")
-    dev = lg.device
+    lg, table, il, ol, mt = _v2_inputs(logits, duration_table, input_length, output_length, max_total)
     B, T, D = lg.shape
-    table = _dev(duration_table, torch.int32, "duration_table").reshape(D)
-    il = _dev(input_length, torch.int32, "input_length").reshape(B)
-    ol = _dev(output_length, torch.int32, "output_length").reshape(B)
-    if max_total is None:
-        max_total = int(ol.max().item()) if B > 0 else 0
-    X = int(max_total) + 1
-    out = dict(out or {})
-    f32 = {"dtype": torch.float32, "name": "float32"}
-    loss = _buf(out, dev, "loss", (B,), **f32)
-    grad = _buf(out, dev, "grad", (B, T, D), want=need_grad, **f32)
-    la = _buf(out, dev, "log_alpha", (B, T + 1, X), want=debug, **f32)
-    lb = _buf(out, dev, "log_beta", (B, T + 1, X), want=debug, **f32)
-    wsb = int(lib.ssnt_v2_fwd_bwd_workspace_size(B, T, int(max_total), bool(test_mode)))
-    ws = _workspace(dev, wsb)
-    st = out.get("status")
-    if st is None:
-        st = _status(dev)
-    else:
-        st.zero_()
-    rc = lib.ssnt_v2_fwd_bwd_device(_p(lg), _p(table), _p(il), _p(ol), B, T, D, int(max_total),
-                                    int(zero_duration_id), bool(allow_skip), bool(test_mode),
-                                    FLAG_ZERO_INFINITY if zero_infinity else 0, _p(loss),
-                                    _p(grad), _p(la), _p(lb), _p(ws), wsb, _p(st), _stream(dev))
-    _finish("v2_fwd_bwd", rc, st, check)
-    res = {"loss": loss, "status": st}
-    if grad is not None:
-        res["grad"] = grad
-    if debug:
-        res["log_alpha"] = la
-        res["log_beta"] = lb
-    return res
+    c = _Call("v2_fwd_bwd", lg.device, out, check)
+    loss = c.buf("loss", (B,))
+    grad = c.buf("grad", (B, T, D), want=need_grad)
+    la = c.buf("log_alpha", (B, T + 1, mt + 1), want=debug)
+    lb = c.buf("log_beta", (B, T + 1, mt + 1), want=debug)
+    c.workspace(lib.ssnt_v2_fwd_bwd_workspace_size, B, T, mt, bool(test_mode))
+    return c.run(lib.ssnt_v2_fwd_bwd_device, lg.data_ptr(), table.data_ptr(), il.data_ptr(),
+                 ol.data_ptr(), B, T, D, mt, int(zero_duration_id), bool(allow_skip), bool(test_mode),
+                 FLAG_ZERO_INFINITY if zero_infinity else 0, loss, grad, la, lb)
 
 
 def v2_viterbi_align(logits, duration_table, input_length, output_length, zero_duration_id, *,
@@ -781,38 +710,18 @@ def v2_viterbi_align(logits, duration_table, input_length, output_length, zero_d
     total). ``need_path=False`` computes ``log_prob`` only. ``out`` may pass preallocated
     tensors under the same keys."""
     lib = load(require_gpu=True)
-    lg = _dev(logits, torch.float32, "logits")
-    dev = lg.device
+    lg, table, il, ol, mt = _v2_inputs(logits, duration_table, input_length, output_length, max_total)
     B, T, D = lg.shape
-    table = _dev(duration_table, torch.int32, "duration_table").reshape(D)
-    il = _dev(input_length, torch.int32, "input_length").reshape(B)
-    ol = _dev(output_length, torch.int32, "output_length").reshape(B)
-    if max_total is None:
-        max_total = int(ol.max().item()) if B > 0 else 0
-    out = dict(out or {})
-    lp = _buf(out, dev, "log_prob", (B,), torch.float32)
-    cls = _buf(out, dev, "duration_class", (B, T), torch.int32, want=need_path)
-    dur = _buf(out, dev, "duration", (B, T), torch.int32, want=need_path)
-    tot = _buf(out, dev, "total", (B,), torch.int32, want=need_path)
-    wsb = int(lib.ssnt_v2_viterbi_align_workspace_size(B, T, int(max_total), bool(test_mode))) \
-        if need_path else 0
-    ws = _workspace(dev, wsb)
-    st = out.get("status")
-    if st is None:
-        st = _status(dev)
-    else:
-        st.zero_()
-    rc = lib.ssnt_v2_viterbi_align_device(_p(lg), _p(table), _p(il), _p(ol), B, T, D,
-                                          int(max_total), int(zero_duration_id), bool(allow_skip),
-                                          bool(test_mode), _p(lp), _p(cls), _p(dur), _p(tot),
-                                          _p(ws), wsb, _p(st), _stream(dev))
-    _finish("v2_viterbi_align", rc, st, check)
-    res = {"log_prob": lp, "status": st}
+    c = _Call("v2_viterbi_align", lg.device, out, check)
+    lp = c.buf("log_prob", (B,))
+    cls = c.buf("duration_class", (B, T), torch.int32, want=need_path)
+    dur = c.buf("duration", (B, T), torch.int32, want=need_path)
+    tot = c.buf("total", (B,), torch.int32, want=need_path)
     if need_path:
-        res["duration_class"] = cls
-        res["duration"] = dur
-        res["total"] = tot
-    return res
+        c.workspace(lib.ssnt_v2_viterbi_align_workspace_size, B, T, mt, bool(test_mode))
+    return c.run(lib.ssnt_v2_viterbi_align_device, lg.data_ptr(), table.data_ptr(), il.data_ptr(),
+                 ol.data_ptr(), B, T, D, mt, int(zero_duration_id), bool(allow_skip), bool(test_mode),
+                 lp, cls, dur, tot)
 
 
 def v2_nbest_align(logits, duration_table, input_length, output_length, zero_duration_id, num_best,
@@ -830,40 +739,22 @@ def v2_nbest_align(logits, duration_table, input_length, output_length, zero_dur
     rank absent. ``need_path=False`` computes ``log_prob`` and ``count`` only. ``out`` may pass
     preallocated tensors under the same keys (not ``count``)."""
     lib = load(require_gpu=True)
-    lg = _dev(logits, torch.float32, "logits")
-    dev = lg.device
+    lg, table, il, ol, mt = _v2_inputs(logits, duration_table, input_length, output_length, max_total)
     B, T, D = lg.shape
     N = int(num_best)
-    table = _dev(duration_table, torch.int32, "duration_table").reshape(D)
-    il = _dev(input_length, torch.int32, "input_length").reshape(B)
-    ol = _dev(output_length, torch.int32, "output_length").reshape(B)
-    if max_total is None:
-        max_total = int(ol.max().item()) if B > 0 else 0
-    out = dict(out or {})
     shape_n = max(N, 0)  # (an N the library refuses: the call below reports it)
-    lp = _buf(out, dev, "log_prob", (B, shape_n), torch.float32)
-    cls = _buf(out, dev, "duration_class", (B, shape_n, T), torch.int32, want=need_path)
-    dur = _buf(out, dev, "duration", (B, shape_n, T), torch.int32, want=need_path)
-    tot = _buf(out, dev, "total", (B, shape_n), torch.int32, want=need_path)
-    wsb = int(lib.ssnt_v2_nbest_align_workspace_size(B, T, int(max_total), bool(test_mode), N)) \
-        if need_path else 0
-    ws = _workspace(dev, wsb)
-    st = out.get("status")
-    if st is None:
-        st = _status(dev)
-    else:
-        st.zero_()
-    rc = lib.ssnt_v2_nbest_align_device(_p(lg), _p(table), _p(il), _p(ol), B, T, D,
-                                        int(max_total), int(zero_duration_id), bool(allow_skip),
-                                        bool(test_mode), N, _p(lp), _p(cls), _p(dur), _p(tot),
-                                        _p(ws), wsb, _p(st), _stream(dev))
-    _finish("v2_nbest_align", rc, st, check)
-    res = {"log_prob": lp, "count": (lp > float("-inf")).sum(dim=1).to(torch.int32), "status": st}
+    c = _Call("v2_nbest_align", lg.device, out, check)
+    lp = c.buf("log_prob", (B, shape_n))
+    cls = c.buf("duration_class", (B, shape_n, T), torch.int32, want=need_path)
+    dur = c.buf("duration", (B, shape_n, T), torch.int32, want=need_path)
+    tot = c.buf("total", (B, shape_n), torch.int32, want=need_path)
     if need_path:
-        res["duration_class"] = cls
-        res["duration"] = dur
-        res["total"] = tot
-    return res
+        c.workspace(lib.ssnt_v2_nbest_align_workspace_size, B, T, mt, bool(test_mode), N)
+    c.run(lib.ssnt_v2_nbest_align_device, lg.data_ptr(), table.data_ptr(), il.data_ptr(),
+          ol.data_ptr(), B, T, D, mt, int(zero_duration_id), bool(allow_skip), bool(test_mode), N,
+          lp, cls, dur, tot)
+    c.res["count"] = (c.res["log_prob"] > float("-inf")).sum(dim=1).to(torch.int32)
+    return c.res
 
 
 def v2_sample_align(logits, duration_table, input_length, output_length, zero_duration_id,
@@ -883,44 +774,19 @@ def v2_sample_align(logits, duration_table, input_length, output_length, zero_du
     sample. ``need_path=False`` writes ``log_prob`` only. ``out`` may pass preallocated tensors
     under the same keys."""
     lib = load(require_gpu=True)
-    lg = _dev(logits, torch.float32, "logits")
-    dev = lg.device
+    lg, table, il, ol, mt = _v2_inputs(logits, duration_table, input_length, output_length, max_total)
     B, T, D = lg.shape
     K = int(num_samples)
-    table = _dev(duration_table, torch.int32, "duration_table").reshape(D)
-    il = _dev(input_length, torch.int32, "input_length").reshape(B)
-    ol = _dev(output_length, torch.int32, "output_length").reshape(B)
-    if max_total is None:
-        max_total = int(ol.max().item()) if B > 0 else 0
-    if uniform is None:
-        un = torch.rand((B, K, T + 1), device=dev, dtype=torch.float32, generator=generator)
-    else:
-        un = _dev(uniform, torch.float32, "uniform")
-        if tuple(un.shape) != (B, K, T + 1):
-            raise ValueError(f"uniform must be (B,K,T+1) = {(B, K, T + 1)}")
-    out = dict(out or {})
-    lp = _buf(out, dev, "log_prob", (B, K), torch.float32)
-    cls = _buf(out, dev, "duration_class", (B, K, T), torch.int32, want=need_path)
-    dur = _buf(out, dev, "duration", (B, K, T), torch.int32, want=need_path)
-    tot = _buf(out, dev, "total", (B, K), torch.int32, want=need_path)
-    wsb = int(lib.ssnt_v2_sample_align_workspace_size(B, T, int(max_total), bool(test_mode), K))
-    ws = _workspace(dev, wsb)
-    st = out.get("status")
-    if st is None:
-        st = _status(dev)
-    else:
-        st.zero_()
-    rc = lib.ssnt_v2_sample_align_device(_p(lg), _p(table), _p(il), _p(ol), _p(un), B, T, D,
-                                         int(max_total), int(zero_duration_id), bool(allow_skip),
-                                         bool(test_mode), K, _p(lp), _p(cls), _p(dur), _p(tot),
-                                         _p(ws), wsb, _p(st), _stream(dev))
-    _finish("v2_sample_align", rc, st, check)
-    res = {"log_prob": lp, "uniform": un, "status": st}
-    if need_path:
-        res["duration_class"] = cls
-        res["duration"] = dur
-        res["total"] = tot
-    return res
+    c = _Call("v2_sample_align", lg.device, out, check)
+    un = c.res["uniform"] = _uniform(uniform, lg.device, (B, K, T + 1), "(B,K,T+1)", generator)
+    lp = c.buf("log_prob", (B, K))
+    cls = c.buf("duration_class", (B, K, T), torch.int32, want=need_path)
+    dur = c.buf("duration", (B, K, T), torch.int32, want=need_path)
+    tot = c.buf("total", (B, K), torch.int32, want=need_path)
+    c.workspace(lib.ssnt_v2_sample_align_workspace_size, B, T, mt, bool(test_mode), K)
+    return c.run(lib.ssnt_v2_sample_align_device, lg.data_ptr(), table.data_ptr(), il.data_ptr(),
+                 ol.data_ptr(), un.data_ptr(), B, T, D, mt, int(zero_duration_id), bool(allow_skip),
+                 bool(test_mode), K, lp, cls, dur, tot)
 
 
 class V2DurationLoss(torch.autograd.Function):
@@ -971,40 +837,20 @@ def v2_expected_cost(logits, cost, duration_table, input_length, output_length, 
     keys."""
     lib = load(require_gpu=True)
     lg = _dev(logits, torch.float32, "logits")
-    dev = lg.device
     B, T, D = lg.shape
     cs = _dev(cost, torch.float32, "cost")
     if tuple(cs.shape) != (B, T, D):
         raise ValueError(f"cost must be (B,T,D) = {(B, T, D)}")
-    table = _dev(duration_table, torch.int32, "duration_table").reshape(D)
-    il = _dev(input_length, torch.int32, "input_length").reshape(B)
-    ol = _dev(output_length, torch.int32, "output_length").reshape(B)
-    if max_total is None:
-        max_total = int(ol.max().item()) if B > 0 else 0
-    out = dict(out or {})
-    f32 = {"dtype": torch.float32, "name": "float32"}
-    risk = _buf(out, dev, "risk", (B,), **f32)
-    loss = _buf(out, dev, "loss", (B,), **f32)
-    gl = _buf(out, dev, "grad_logits", (B, T, D), want=need_grad, **f32)
-    gc = _buf(out, dev, "grad_cost", (B, T, D), want=need_grad, **f32)
-    wsb = int(lib.ssnt_v2_expected_cost_workspace_size(B, T, int(max_total), bool(test_mode),
-                                                       bool(need_grad)))
-    ws = _workspace(dev, wsb)
-    st = out.get("status")
-    if st is None:
-        st = _status(dev)
-    else:
-        st.zero_()
-    rc = lib.ssnt_v2_expected_cost_device(_p(lg), _p(cs), _p(table), _p(il), _p(ol), B, T, D,
-                                          int(max_total), int(zero_duration_id), bool(allow_skip),
-                                          bool(test_mode), _p(risk), _p(loss), _p(gl), _p(gc),
-                                          _p(ws), wsb, _p(st), _stream(dev))
-    _finish("v2_expected_cost", rc, st, check)
-    res = {"risk": risk, "loss": loss, "status": st}
-    if need_grad:
-        res["grad_logits"] = gl
-        res["grad_cost"] = gc
-    return res
+    lg, table, il, ol, mt = _v2_inputs(lg, duration_table, input_length, output_length, max_total)
+    c = _Call("v2_expected_cost", lg.device, out, check)
+    risk = c.buf("risk", (B,))
+    loss = c.buf("loss", (B,))
+    gl = c.buf("grad_logits", (B, T, D), want=need_grad)
+    gc = c.buf("grad_cost", (B, T, D), want=need_grad)
+    c.workspace(lib.ssnt_v2_expected_cost_workspace_size, B, T, mt, bool(test_mode), bool(need_grad))
+    return c.run(lib.ssnt_v2_expected_cost_device, lg.data_ptr(), cs.data_ptr(), table.data_ptr(),
+                 il.data_ptr(), ol.data_ptr(), B, T, D, mt, int(zero_duration_id), bool(allow_skip),
+                 bool(test_mode), risk, loss, gl, gc)
 
 
 class V2ExpectedCost(torch.autograd.Function):

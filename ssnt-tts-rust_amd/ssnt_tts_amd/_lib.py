@@ -135,6 +135,8 @@ def _bind(path: Path, sigs) -> ctypes.CDLL:
         raise RuntimeError(f"{path.name} not found at {path}: build it with `make` "
                            "(there is no CPU fallback)")
     lib = ctypes.CDLL(str(path))
+    # every symbol gets its argtypes: the mirror's lattice calls pass pointers as plain integer
+    # addresses, which ctypes would truncate to a C int on a symbol bound without them
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
         fn.restype = res

@@ -27,6 +27,7 @@ import sample_cases as SC
 import v2_viterbi_ref as V2R
 import viterbi_ref as VR
 from f4_cases import random_case
+from gpu_util import DEV, _t
 from loss_sum_ref import wave_order_sum
 from test_gpu_fwd_bwd import _assert_bit_exact, _check_debug64
 from test_gpu_sample_align import _check as _check_sample
@@ -39,7 +40,6 @@ from test_gpu_viterbi import _same as _same_viterbi
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 F32, I32, U8 = torch.float32, torch.int32, torch.uint8
 F_TERM, F_ZINF = 1, 2
 BAD_LENGTH_BIT = 4  # kStatusBadLength (ssnt_status_from_bits -> SSNT_ERR_BAD_LENGTH = 7)
@@ -563,11 +563,6 @@ def _nan_like(shape, dtype):
     t = torch.empty(shape, dtype=dtype, device=DEV)
     t.view(-1).view(I32).fill_(0x7FC00000)  # a NaN as f32; as i32 a value no output holds
     return t
-
-
-def _t(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).to(DEV)
 
 
 def test_mirror_outputs_fwd_bwd(gpu, oracle):

@@ -10,14 +10,9 @@ import pytest
 import torch
 
 import decode_cases as dc
+from gpu_util import _t
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-
-
-def _t(x, dt=None):
-    t = torch.from_numpy(np.ascontiguousarray(x))
-    return (t if dt is None else t.to(dt)).to(DEV)
 
 
 def _eq(gpu_out, ref, keys, ctx=""):

@@ -16,10 +16,10 @@ import torch
 import contract_cases as CC
 import duration_posterior_cases as DC
 import guarded as G
+from gpu_util import DEV, _t
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 F32, I32, U8 = torch.float32, torch.int32, torch.uint8
 BAD_LENGTH_BIT = 4
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE = 1, 5, 6
@@ -32,10 +32,6 @@ TOL = {
 # tests/test_gpu_expected_cost.py TOL["grad_cost"]: the edge posterior of ssnt_expected_cost
 # against float64, for the mean-duration identity, which compares two f32 results
 GRAD_COST_TOL = 8e-6
-
-
-def _t(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _run(gpu, c, out=None, check=False, D=None):

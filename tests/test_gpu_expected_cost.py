@@ -15,10 +15,10 @@ import contract_cases as CC
 import expected_cost_cases as EC
 import expected_cost_ref as R
 import guarded as G
+from gpu_util import DEV, _t
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 F32, I32, U8 = torch.float32, torch.int32, torch.uint8
 BAD_LENGTH_BIT = 4
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE = 1, 5, 6
@@ -34,10 +34,6 @@ TOL = {
 # ssnt_fwd_bwd against float64 (5.6e-6 relative on alpha at the largest BASELINE
 # shape; the shapes here are far smaller), for the cross-checks that compare two f32 results
 FWD_BWD_TOL = 5.6e-6
-
-
-def _t(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _run(gpu, c, need_grad=True, out=None, check=False):

@@ -5,21 +5,16 @@ Bit-exact on every per-step output and every path output; "no candidate" (the re
 panic, src/v2.rs:292) must be reported for the same inputs."""
 import numpy as np
 import pytest
-import torch
 
 import decode_cases as dc
+from gpu_util import _t
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 V2_OUT = ("prediction", "log_prob", "next_t", "next_u", "next_is_finished", "next_total_duration",
           "beam_branch", "ordered_beam_branch", "path_prediction", "duration")
 TONE_OUT = ("prediction", "log_prob", "next_t", "next_u", "next_is_finished", "beam_branch",
             "ordered_beam_branch", "path_prediction")
-
-
-def _t(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
 
 
 @pytest.fixture(autouse=True, params=[pytest.param(0, id="rank")])

@@ -4,7 +4,6 @@ layout and list width the envelope admits, ragged extents, 8-byte-aligned inputs
 zero-probability lattices, utterances with fewer than N paths, both backpointer stores (LDS,
 workspace); plus checks that use no DP (brute force, the sibling kernels, path invariants), the
 input contract (dead cells, guarded buffers, stale bytes) and the error paths."""
-import ctypes
 import functools
 from math import comb
 
@@ -15,18 +14,13 @@ import torch
 import contract_cases as CC
 import guarded as G
 import nbest_ref as NR
+from gpu_util import DEV, switch_point, _t, vp
 from test_gpu_viterbi import _lattice, _ragged
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 OUTS = ("log_prob", "position", "duration")
 INVALID, UNSUPPORTED, WORKSPACE, BAD_LENGTH = 1, 5, 6, 7
-
-
-def _t(x, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(x))
-    return (t if dtype is None else t.to(dtype)).to(DEV)
 
 
 def _run(gpu, lt, S, P, N, lo=None, terminal=True, **kw):
@@ -171,13 +165,7 @@ def test_zero_probability_transitions(gpu):
 # ---- 7. backpointer storage ------------------------------------------------------------------
 def _switch_T(gpu, U, N):
     """The largest T whose backpointers stay in LDS at width U and N ranks (by the size query)."""
-    q = gpu.load().ssnt_nbest_align_workspace_size
-    lo, hi = 1, 1 << 16
-    assert q(1, lo, U, N) == 0 and q(1, hi, U, N) > 0
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        lo, hi = (mid, hi) if q(1, mid, U, N) == 0 else (lo, mid)
-    return lo
+    return switch_point(lambda T: gpu.load().ssnt_nbest_align_workspace_size(1, T, U, N))
 
 
 def _c_call(lib, v, B, T, U, N, ws, wsb, flags=1, paths=True):
@@ -330,7 +318,6 @@ def test_error_returns(gpu):
     p = torch.full((B,), U, dtype=torch.int32, device=DEV)
     lp = torch.full((B, 8), 7.0, device=DEV)
     st = torch.zeros(1, dtype=torch.int32, device=DEV)
-    vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
 
     def call(lt=x, sl=s, pl=p, b=B, t=T, u=U, n=N, flags=1, out=lp):
         return lib.ssnt_nbest_align_device(vp(lt), None, vp(sl), vp(pl), b, t, u, n, flags, vp(out), None, None,

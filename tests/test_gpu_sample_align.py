@@ -3,8 +3,6 @@ the float64 reference of tests/sample_ref.py. Every case checks: each returned p
 monotone path with matching durations; log_prob is bit-equal to the sequential f32 sum of the
 returned path; every *clear* sample (reference margin > 1e-4) has exactly the reference's path; the
 share of unclear samples stays within the cap that tests/test_sample_ref.py asserts on the CPU."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -12,16 +10,11 @@ import torch
 import sample_cases as SC
 import sample_ref as SR
 import value_cases as VC
+from gpu_util import DEV, _t, vp
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 INVALID, UNSUPPORTED, WORKSPACE, BAD_LENGTH = 1, 5, 6, 7
-
-
-def _t(x, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(x))
-    return (t if dtype is None else t.to(dtype)).to(DEV)
 
 
 def _args(c):
@@ -182,7 +175,6 @@ def test_errors(gpu):
     pos = torch.full((B, 64, T), 9, dtype=torch.int32, device=DEV)
     dur = torch.full((B, 64, U), 9, dtype=torch.int32, device=DEV)
     st = torch.zeros(1, dtype=torch.int32, device=DEV)
-    vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
 
     def call(lt=x, sl=s, pl=p, u=un, b=B, t=T, w=U, k=K, flags=1, out=lp, ws=None, wsb=0):
         return lib.ssnt_sample_align_device(vp(lt), vp(o), vp(sl), vp(pl), vp(u), b, t, w, k, flags,

@@ -6,7 +6,6 @@ columns, guards, workspace contents, refused calls), determinism and autograd. E
 normalised as tests/v2_expected_cost_cases.py `errors` does; the tolerances are 4x the worst value
 tools/bench_v2_expected_cost.py --accuracy measured (profiles/v2_expected_cost_accuracy.jsonl, line
 "worst"), rounded up to one significant digit."""
-import ctypes
 import functools
 
 import numpy as np
@@ -16,10 +15,10 @@ import torch
 import contract_cases as CC
 import v2_expected_cost_cases as EC
 import v2_expected_cost_ref as R
+from gpu_util import DEV, _t, vp
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 F32, I32, U8 = torch.float32, torch.int32, torch.uint8
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_BAD_LENGTH, ERR_BAD_INDEX = 1, 5, 6, 7, 8
 
@@ -32,13 +31,6 @@ TOL = {
 }
 # (the large shape, B=64 I=400 O=2000 D=16, enters "worst" with the first 8 of its 64 utterances
 # compared against the float64 reference; its largest value is risk 1.29e-7, entropy cost, band mode)
-
-
-def _t(a, dtype=None):
-    if a is None:
-        return None
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).to(DEV)
 
 
 def _args(c):
@@ -330,7 +322,6 @@ def test_refusals_write_nothing(gpu):
     o = {k: torch.full(s, 7.0, device=DEV) for k, s in (("risk", (B,)), ("loss", (B,)), ("gl", (B, T, D)),
                                                          ("gc", (B, T, D)))}
     st = torch.full((1,), 5, dtype=I32, device=DEV)
-    vp = lambda t: None if t is None else ctypes.c_void_p(t if isinstance(t, int) else t.data_ptr())  # noqa: E731
 
     def call(lg=x, c=cs, table=tb, i=il, ol_=ol, b=B, t=T, d=D, m=mt, test=False, risk=o["risk"], loss=o["loss"],
              gl=o["gl"], gc=o["gc"], w=ws, wsb=need):

@@ -9,9 +9,9 @@ import pytest
 import torch
 
 from f4_cases import random_case
+from gpu_util import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
 def _run(gpu, logits, table, I, O, zid=0, allow_skip=True, test_mode=False, max_total=None,

@@ -5,7 +5,6 @@ every class padding, the unrolled and the rolled class loop, both backpointer st
 entry widths, tie-rich and edge inputs, at the configs[4] row shape, plus N = 1 against
 v2_viterbi_align, the independence of a rank from the list width, invariants that do not use the
 DP, and the API / error paths."""
-import ctypes
 import functools
 
 import numpy as np
@@ -16,18 +15,13 @@ import f4_cases
 import guarded as G
 import v2_nbest_ref as NR
 import v2_viterbi_ref as VR
+from gpu_util import DEV, poisoned_runs, switch_point, _t, vp
 from test_gpu_v2_viterbi import F4_TABLES, _edge_inputs, _medium, _softmax_logits
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 KEYS = ("duration_class", "duration", "total")
 OUTS = ("log_prob",) + KEYS
-
-
-def _t(x, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(x))
-    return (t if dtype is None else t.to(dtype)).to(DEV)
 
 
 def _run(gpu, logits, table, I, O, max_total, N, zid=0, allow_skip=True, test_mode=False, **kw):
@@ -210,12 +204,7 @@ def test_tie_rich(gpu, test_mode, N):
 def _switch_I(gpu, max_total, test_mode, N):
     """The largest max_steps whose backpointers stay in LDS (by the size query)."""
     q = gpu.load().ssnt_v2_nbest_align_workspace_size
-    lo, hi = 1, 1 << 20
-    assert q(1, lo, max_total, test_mode, N) == 0 and q(1, hi, max_total, test_mode, N) > 0
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        lo, hi = (mid, hi) if q(1, mid, max_total, test_mode, N) == 0 else (lo, mid)
-    return lo
+    return switch_point(lambda I: q(1, I, max_total, test_mode, N), hi=1 << 20)
 
 
 def _poisoned(gpu, logits, table, I, O, mt, test_mode, N):
@@ -233,22 +222,14 @@ def _poisoned(gpu, logits, table, I, O, mt, test_mode, N):
                                "total": ((B, N), i32), "status": ((1,), i32), "ws": ((need,), torch.uint8)})
     for k, a in (("table", table), ("il", I), ("ol", O)):
         G.put(v[k], np.asarray(a, np.int32))
-    res = []
-    for fill in (0xFF, 0x00, "stale"):
-        for x in ([logits] if fill != "stale" else [logits[::-1, ::-1], logits]):  # stale: other logits first
-            G.put(v["lg"], np.ascontiguousarray(x, np.float32))
-            if fill != "stale":
-                G.fill_bytes(v["ws"], fill)
-            v["status"].zero_()
-            rc = G.call(lib, "ssnt_v2_nbest_align_device", v["lg"], v["table"], v["il"], v["ol"], B, T, D,
-                        int(mt), 0, True, bool(test_mode), N, v["log_prob"], v["duration_class"], v["duration"],
-                        v["total"], v["ws"], need, v["status"], torch.cuda.current_stream().cuda_stream)
-            assert rc == 0
-            torch.cuda.synchronize()
-            assert int(v["status"].item()) == 0
-            arena.check()
-        res.append({k: G.get(v[k]) for k in OUTS})
-    return res
+
+    def call():
+        return G.call(lib, "ssnt_v2_nbest_align_device", v["lg"], v["table"], v["il"], v["ol"], B, T, D,
+                      int(mt), 0, True, bool(test_mode), N, v["log_prob"], v["duration_class"], v["duration"],
+                      v["total"], v["ws"], need, v["status"], torch.cuda.current_stream().cuda_stream)
+
+    return poisoned_runs(arena, v, lambda x: G.put(v["lg"], np.ascontiguousarray(x, np.float32)), call, logits,
+                         logits[::-1, ::-1], OUTS)
 
 
 @pytest.mark.parametrize("N", [1, 4])
@@ -392,7 +373,6 @@ def test_error_returns_write_nothing(gpu):
     lp = torch.full((B, N), 7.0, device=DEV)
     tot = torch.full((B, N), 9, dtype=torch.int32, device=DEV)
     st = torch.zeros(1, dtype=torch.int32, device=DEV)
-    vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
 
     def call(lg=x, table=tb, i=il, o=ol, b=B, t=T, d=D, m=mt, test=False, n=N, out=lp, cls=None, ws=None,
              wsb=0):

@@ -5,8 +5,6 @@ every sample, clear or not, must be an admissible sequence (f4_cases.move_ok per
 log_prob is the sequential f32 sum of its class log-probs, bit for bit, and no larger than the
 best path's (v2_viterbi_align). Plus frequencies against the enumerated posterior, the infeasible
 rule, the clamp, every refusal, a poisoned workspace, the Python surface and two streams."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -15,16 +13,11 @@ import f4_cases
 import guarded as G
 import v2_sample_ref as SR
 import v2_viterbi_ref as VR
+from gpu_util import DEV, poisoned_runs, _t, vp
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 OUT_KEYS = ("log_prob", "duration_class", "duration", "total")
-
-
-def _t(x, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(x))
-    return (t if dtype is None else t.to(dtype)).to(DEV)
 
 
 def _args(case):
@@ -259,7 +252,6 @@ def test_refusals_write_nothing(gpu):
     ints = {k: torch.full(s, 9, dtype=torch.int32, device=DEV)
             for k, s in (("cls", (B, K, T)), ("dur", (B, K, T)), ("tot", (B, K)))}
     st = torch.full((1,), 5, dtype=torch.int32, device=DEV)
-    vp = lambda t: None if t is None else ctypes.c_void_p(t if isinstance(t, int) else t.data_ptr())  # noqa: E731
 
     def call(lg=x, table=tb, i=il, o=ol, u=un, b=B, t=T, d=D, m=mt, test=False, k=K, out=lp, w=ws, wsb=need):
         return lib.ssnt_v2_sample_align_device(vp(lg), vp(table), vp(i), vp(o), vp(u), b, t, d, m, 0, True, test, k,
@@ -303,21 +295,14 @@ def test_poisoned_workspace(gpu, test_mode):
     for k, a in (("table", table), ("il", I), ("ol", O)):
         G.put(v[k], np.asarray(a, np.int32))
     G.put(v["un"], u)
-    res = []
-    for fill in (0xFF, 0x00, "stale"):
-        for x in ([logits] if fill != "stale" else [logits[::-1, ::-1], logits]):  # stale: other logits first
-            G.put(v["lg"], np.ascontiguousarray(x, np.float32))
-            if fill != "stale":
-                G.fill_bytes(v["ws"], fill)
-            v["status"].zero_()
-            rc = G.call(lib, "ssnt_v2_sample_align_device", v["lg"], v["table"], v["il"], v["ol"], v["un"], B, T, D,
-                        int(mt), 0, bool(allow_skip), bool(test_mode), K, v["log_prob"], v["duration_class"],
-                        v["duration"], v["total"], v["ws"], need, v["status"], torch.cuda.current_stream().cuda_stream)
-            assert rc == 0
-            torch.cuda.synchronize()
-            assert int(v["status"].item()) == 0
-            arena.check()
-        res.append({k: G.get(v[k]) for k in OUT_KEYS})
+
+    def call():
+        return G.call(lib, "ssnt_v2_sample_align_device", v["lg"], v["table"], v["il"], v["ol"], v["un"], B, T, D,
+                      int(mt), 0, bool(allow_skip), bool(test_mode), K, v["log_prob"], v["duration_class"],
+                      v["duration"], v["total"], v["ws"], need, v["status"], torch.cuda.current_stream().cuda_stream)
+
+    res = poisoned_runs(arena, v, lambda x: G.put(v["lg"], np.ascontiguousarray(x, np.float32)), call, logits,
+                        logits[::-1, ::-1], OUT_KEYS)
     for r in res[1:]:
         for k in OUT_KEYS:
             assert r[k].tobytes() == res[0][k].tobytes(), k

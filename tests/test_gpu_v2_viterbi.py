@@ -4,7 +4,6 @@ duration and total value-identical (np.array_equal), on both cell forms, every c
 both backpointer stores (LDS, workspace), tie-rich and edge inputs, at the configs[4] shape
 against a planted path, plus invariants that do not use the DP, the round trip through
 upsample_source_indexes, and the API / error paths."""
-import ctypes
 import functools
 
 import numpy as np
@@ -14,16 +13,11 @@ import torch
 import f4_cases
 import guarded as G
 import v2_viterbi_ref as VR
+from gpu_util import DEV, poisoned_runs, switch_point, _t, vp
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 KEYS = ("duration_class", "duration", "total")
-
-
-def _t(x, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(x))
-    return (t if dtype is None else t.to(dtype)).to(DEV)
 
 
 def _run(gpu, logits, table, I, O, max_total, zid=0, allow_skip=True, test_mode=False, **kw):
@@ -205,12 +199,7 @@ def test_tie_rich(gpu, test_mode):
 def _switch_I(gpu, max_total, test_mode):
     """The largest max_steps whose backpointers stay in LDS (by the size query)."""
     q = gpu.load().ssnt_v2_viterbi_align_workspace_size
-    lo, hi = 1, 1 << 20
-    assert q(1, lo, max_total, test_mode) == 0 and q(1, hi, max_total, test_mode) > 0
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        lo, hi = (mid, hi) if q(1, mid, max_total, test_mode) == 0 else (lo, mid)
-    return lo
+    return switch_point(lambda I: q(1, I, max_total, test_mode), hi=1 << 20)
 
 
 def _poisoned(gpu, logits, table, I, O, mt, test_mode):
@@ -228,22 +217,14 @@ def _poisoned(gpu, logits, table, I, O, mt, test_mode):
                                "ws": ((need,), torch.uint8)})
     for k, a in (("table", table), ("il", I), ("ol", O)):
         G.put(v[k], np.asarray(a, np.int32))
-    res = []
-    for fill in (0xFF, 0x00, "stale"):
-        for x in ([logits] if fill != "stale" else [logits[::-1, ::-1], logits]):  # stale: other logits first
-            G.put(v["lg"], np.ascontiguousarray(x, np.float32))
-            if fill != "stale":
-                G.fill_bytes(v["ws"], fill)
-            v["status"].zero_()
-            rc = G.call(lib, "ssnt_v2_viterbi_align_device", v["lg"], v["table"], v["il"], v["ol"], B, T, D,
-                        int(mt), 0, True, bool(test_mode), v["log_prob"], v["duration_class"], v["duration"],
-                        v["total"], v["ws"], need, v["status"], torch.cuda.current_stream().cuda_stream)
-            assert rc == 0
-            torch.cuda.synchronize()
-            assert int(v["status"].item()) == 0
-            arena.check()
-        res.append({k: G.get(v[k]) for k in ("log_prob", "duration_class", "duration", "total")})
-    return res
+
+    def call():
+        return G.call(lib, "ssnt_v2_viterbi_align_device", v["lg"], v["table"], v["il"], v["ol"], B, T, D,
+                      int(mt), 0, True, bool(test_mode), v["log_prob"], v["duration_class"], v["duration"],
+                      v["total"], v["ws"], need, v["status"], torch.cuda.current_stream().cuda_stream)
+
+    return poisoned_runs(arena, v, lambda x: G.put(v["lg"], np.ascontiguousarray(x, np.float32)), call, logits,
+                         logits[::-1, ::-1], ("log_prob", "duration_class", "duration", "total"))
 
 
 @pytest.mark.parametrize("test_mode,mt", [(True, 300), (False, 2000)], ids=["test_mode", "band"])
@@ -396,7 +377,6 @@ def test_error_returns(gpu):
     ol = torch.full((B,), mt, dtype=torch.int32, device=DEV)
     lp = torch.empty(B, device=DEV)
     st = torch.zeros(1, dtype=torch.int32, device=DEV)
-    vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
 
     def call(lg=x, table=tb, i=il, o=ol, b=B, t=T, d=D, m=mt, test=False, out=lp, cls=None, ws=None, wsb=0):
         return lib.ssnt_v2_viterbi_align_device(vp(lg), vp(table), vp(i), vp(o), b, t, d, m, 0, True, test,

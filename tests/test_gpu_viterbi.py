@@ -3,8 +3,6 @@ of tests/viterbi_ref.py: log_prob, position and duration bit / value identical (
 on every lane layout (K = 1, 2, 4, 8, 16), ragged extents, 8-byte-aligned inputs, tie-rich and
 zero-probability lattices, both backpointer stores (LDS, workspace), plus invariants that do not
 use the DP, the round trip through upsample_source_indexes, and the error paths."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -12,15 +10,9 @@ import torch
 import guarded as G
 import lattice_ref
 import viterbi_ref as VR
+from gpu_util import DEV, poisoned_runs, switch_point, _t, vp
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-
-
-def _t(x, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(x))
-    return (t if dtype is None else t.to(dtype)).to(DEV)
 
 
 def _run(gpu, lt, S, P, lo=None, terminal=True, **kw):
@@ -129,14 +121,7 @@ def test_zero_probability_transitions(gpu):
 # ---- 5. backpointer storage ------------------------------------------------------------------
 def _switch_T(gpu, U):
     """The largest T whose backpointer bits stay in LDS at width U (by the size query)."""
-    lib = gpu.load()
-    lo, hi = 1, 1 << 16
-    assert lib.ssnt_viterbi_align_workspace_size(1, lo, U) == 0
-    assert lib.ssnt_viterbi_align_workspace_size(1, hi, U) > 0
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        lo, hi = (mid, hi) if lib.ssnt_viterbi_align_workspace_size(1, mid, U) == 0 else (lo, mid)
-    return lo
+    return switch_point(lambda T: gpu.load().ssnt_viterbi_align_workspace_size(1, T, U))
 
 
 def _poisoned(gpu, lt, S, P):
@@ -153,22 +138,14 @@ def _poisoned(gpu, lt, S, P):
                                "status": ((1,), i32), "ws": ((need,), torch.uint8)})
     G.put(v["sl"], np.asarray(S, np.int32))
     G.put(v["pl"], np.asarray(P, np.int32))
-    res = []
-    for fill in (0xFF, 0x00, "stale"):
-        for x in ([lt] if fill != "stale" else [lt[::-1, ::-1], lt]):  # stale: another lattice first
-            G.put(v["lt"], np.ascontiguousarray(x))
-            if fill != "stale":
-                G.fill_bytes(v["ws"], fill)
-            v["status"].zero_()
-            rc = G.call(lib, "ssnt_viterbi_align_device", v["lt"], None, v["sl"], v["pl"], B, T, U, 1,
-                        v["log_prob"], v["position"], v["duration"], v["ws"], need, v["status"],
-                        torch.cuda.current_stream().cuda_stream)
-            assert rc == 0
-            torch.cuda.synchronize()
-            assert int(v["status"].item()) == 0
-            arena.check()
-        res.append({k: G.get(v[k]) for k in ("log_prob", "position", "duration")})
-    return res
+
+    def call():
+        return G.call(lib, "ssnt_viterbi_align_device", v["lt"], None, v["sl"], v["pl"], B, T, U, 1,
+                      v["log_prob"], v["position"], v["duration"], v["ws"], need, v["status"],
+                      torch.cuda.current_stream().cuda_stream)
+
+    return poisoned_runs(arena, v, lambda x: G.put(v["lt"], np.ascontiguousarray(x)), call, lt, lt[::-1, ::-1],
+                         ("log_prob", "position", "duration"))
 
 
 @pytest.mark.parametrize("U", [130, 400])
@@ -255,7 +232,6 @@ def test_error_returns(gpu):
     p = torch.full((B,), U, dtype=torch.int32, device=DEV)
     lp = torch.empty(B, device=DEV)
     st = torch.zeros(1, dtype=torch.int32, device=DEV)
-    vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
 
     def call(lt=x, sl=s, pl=p, b=B, t=T, u=U, flags=1, out=lp, ws=None, wsb=0, pos=None):
         return lib.ssnt_viterbi_align_device(vp(lt), None, vp(sl), vp(pl), b, t, u, flags, vp(out),

@@ -136,3 +136,47 @@ def test_call_follows_the_signature_table():
     with pytest.raises(AssertionError):  # None where the signature has an int
         G.call(Lib(), "ssnt_viterbi_align_device", v["x"], None, v["n"], v["n"], None, 2, 2, 1, v["x"],
                None, None, None, 0, None, None)
+
+
+# ---- gpu_util.poisoned_runs over stub entries: what the GPU tests rely on it to catch ----------
+def _stub_runs(entry):
+    """poisoned_runs of `entry(arena, v)` over an arena with an input, an output, a status word and a
+    workspace; x and `other` differ."""
+    from gpu_util import poisoned_runs
+    arena, v = G.lay_out("cpu", {"x": ((8,), torch.float32), "y": ((8,), torch.float32),
+                                 "status": ((1,), torch.int32), "ws": ((64,), torch.uint8)})
+    x = np.arange(8, dtype=np.float32)
+    return poisoned_runs(arena, v, lambda a: G.put(v["x"], a), lambda: entry(arena, v) or 0, x, x[::-1].copy(),
+                         ("y",))
+
+
+def test_poisoned_runs_of_a_pure_entry_agree():
+    def pure(arena, v):  # writes its workspace before reading it
+        v["ws"][:32].view(torch.float32).copy_(v["x"] * 2)
+        v["y"].copy_(v["ws"][:32].view(torch.float32) + 1)
+
+    res = _stub_runs(pure)
+    assert len(res) == 3 and np.array_equal(res[0]["y"], np.arange(8, dtype=np.float32) * 2 + 1)
+    assert all(r["y"].tobytes() == res[0]["y"].tobytes() for r in res[1:])
+
+
+def test_poisoned_runs_show_a_workspace_byte_read_before_written():
+    def leaky(arena, v):  # byte 40 of the workspace reaches the output unwritten
+        v["y"].copy_(v["x"])
+        v["y"][0] = float(v["ws"][40])
+        v["ws"][40] = int(v["x"][0]) + 1
+
+    res = _stub_runs(leaky)
+    assert [float(r["y"][0]) for r in res] == [255.0, 0.0, 8.0]  # the fill, the fill, the other input's run
+    assert len({r["y"].tobytes() for r in res}) == 3
+
+
+def test_poisoned_runs_catch_a_write_past_the_workspace():
+    def overrun(arena, v):  # one byte past the workspace's last byte
+        v["y"].copy_(v["x"])
+        blk = next(b for b in arena.blocks if b["name"] == "ws")
+        arena.buf[blk["end"]] = 0x11
+
+    with pytest.raises(AssertionError) as e:
+        _stub_runs(overrun)
+    assert "guard after block 'ws'" in str(e.value) and "1 bytes after" in str(e.value), str(e.value)
