@@ -14,7 +14,7 @@ ORACLE    := oracle/build/libssnt_oracle.so
 # the CPU oracle reproduces it bit for bit. Correctly rounded f32 division is HIP's default.
 HIPFLAGS  := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -Wall \
              -Wno-unused-function -I include -I $(CSRC)
-HIP_SRCS  := $(CSRC)/fwd_bwd_dispatch.hip $(CSRC)/fwd_bwd.hip $(CSRC)/fwd_bwd_stream.hip $(CSRC)/fwd_bwd_wide.hip $(CSRC)/v2_fwd_bwd.hip $(CSRC)/v2_viterbi.hip \
+HIP_SRCS  := $(CSRC)/fwd_bwd_dispatch.hip $(CSRC)/fwd_bwd.hip $(CSRC)/fwd_bwd_stream.hip $(CSRC)/fwd_bwd_wide.hip $(CSRC)/fwd_bwd_band.hip $(CSRC)/v2_fwd_bwd.hip $(CSRC)/v2_viterbi.hip \
              $(CSRC)/v2_sample_align.hip $(CSRC)/v2_nbest_align.hip \
              $(CSRC)/decode.hip $(CSRC)/viterbi.hip $(CSRC)/sample_align.hip $(CSRC)/nbest_align.hip \
              $(CSRC)/expected_cost.hip $(CSRC)/duration_posterior.hip $(CSRC)/v2_expected_cost.hip \

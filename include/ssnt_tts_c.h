@@ -99,7 +99,8 @@ typedef enum {
   SSNT_ERR_WORKSPACE = 6,         /* workspace missing / too small */
   SSNT_ERR_BAD_LENGTH = 7,        /* a length exceeds the tensor extent */
   SSNT_ERR_BAD_INDEX = 8,         /* backtrace branch index outside [0, W) */
-  SSNT_ERR_INTERNAL = 9           /* fwd-bwd: a bounded intra-kernel wait expired (a bug) */
+  SSNT_ERR_INTERNAL = 9,          /* fwd-bwd: a bounded intra-kernel wait expired (a bug) */
+  SSNT_ERR_BAD_BAND = 10          /* banded fwd-bwd: band_start is not a valid band */
 } ssnt_status;
 
 const char *ssnt_status_string(int status);
@@ -175,6 +176,36 @@ int ssnt_fwd_bwd_debug64_device(const float *log_trans, const float *log_obs, co
                                 int flags, double *loss, float *grad_trans, float *grad_obs,
                                 double *log_alpha, double *log_beta, void *workspace,
                                 size_t workspace_bytes, int *status, void *stream);
+/* ---- forward-backward on a band of the emit/shift lattice ----
+ * The lattice of ssnt_fwd_bwd_device with every cell outside a band removed: at step s only the
+ * band_width = R columns p = band_start[b,s] + r, r in [0, R), exist. log_trans_band (B,T,R,2),
+ * log_obs_band (B,T,R) (NULL = none) and the gradients hold band cell (s,r) = lattice cell
+ * (s, band_start[b,s] + r); band_start (B,T) i32; step_len S_b <= T and pos_len P_b (no max_pos:
+ * the dense lattice is never formed). A band is valid when band_start[b,0] == 0, every
+ * band_start[b,s+1] - band_start[b,s] is 0 or 1 (s + 1 < S_b), and the last window holds the last
+ * position: band_start[b,S_b-1] <= P_b - 1 < band_start[b,S_b-1] + R. Outputs: loss (B) = -ln of
+ * the mass of the paths inside the band; grad_band (B,T,R,2) and grad_obs_band (B,T,R) its
+ * gradients (NULL = skip), bit for bit those of ssnt_fwd_bwd_device on the dense lattice that is
+ * -inf outside the band and on the two kinds of edges that leave it: the shift out of r = R-1
+ * when the band stays, the emit out of r = 0 when it moves. Those edges get gradient +0.
+ * Never read into a result: what ssnt_fwd_bwd_device never reads (with p = band_start + r; columns
+ * at p >= P_b are dead), the band-leaving edges, and band_start at steps >= S_b. Infeasible
+ * utterances, bad lengths (S_b > T or a negative length: SSNT_ERR_BAD_LENGTH in `status`) and the
+ * flags as ssnt_fwd_bwd_device. An invalid band makes its utterance infeasible (loss +inf, or 0
+ * with SSNT_FLAG_ZERO_INFINITY; gradients 0) and sets SSNT_ERR_BAD_BAND in `status`; it is refused
+ * by comparisons alone and the other utterances are unaffected. band_width outside [1, 256] and
+ * a max_steps whose band_start does not fit LDS (above about 39000) return SSNT_ERR_UNSUPPORTED.
+ * `workspace` holds ssnt_fwd_bwd_band_workspace_size() bytes when a gradient is requested: 0 (NULL
+ * workspace) while the rows of both sweeps fit LDS, else 8 bytes per band cell; missing or short:
+ * SSNT_ERR_WORKSPACE. Without gradients no workspace is needed and loss has the same bits. A
+ * refused call writes nothing. Device pointers, asynchronous on `stream`. New: the reference has
+ * no forward-backward. */
+size_t ssnt_fwd_bwd_band_workspace_size(int batch, int max_steps, int band_width);
+int ssnt_fwd_bwd_band_device(const float *log_trans_band, const float *log_obs_band,
+                             const int *band_start, const int *step_len, const int *pos_len,
+                             int batch, int max_steps, int band_width, int flags, float *loss,
+                             float *grad_band, float *grad_obs_band, void *workspace,
+                             size_t workspace_bytes, int *status, void *stream);
 /* Host-pointer variant (synchronous; copies through the calling thread's GPU context). */
 int ssnt_fwd_bwd(const float *log_trans, const float *log_obs, const int *step_len,
                  const int *pos_len, int batch, int max_steps, int max_pos, int flags,

@@ -25,6 +25,7 @@ int status_bits_to_code(int bits) {
   if (bits & kStatusDurationMismatch) return SSNT_ERR_DURATION_MISMATCH;
   if (bits & kStatusBadLength) return SSNT_ERR_BAD_LENGTH;
   if (bits & kStatusBadIndex) return SSNT_ERR_BAD_INDEX;
+  if (bits & kStatusBadBand) return SSNT_ERR_BAD_BAND;
   if (bits & (kStatusTimeout | kStatusRingTag)) return SSNT_ERR_INTERNAL;  // (tags: diag builds)
   return SSNT_OK;
 }
@@ -477,6 +478,7 @@ const char* ssnt_status_string(int status) {
     case SSNT_ERR_BAD_LENGTH: return "length exceeds tensor extent";
     case SSNT_ERR_BAD_INDEX: return "beam branch index out of range";
     case SSNT_ERR_INTERNAL: return "internal: a bounded intra-kernel wait expired";
+    case SSNT_ERR_BAD_BAND: return "band_start is not a valid band";
     default: return "unknown status";
   }
 }
@@ -837,6 +839,24 @@ int ssnt_fwd_bwd_sum_device(const float* log_trans, const float* log_obs, const 
                               workspace_bytes, status);
   a.loss_sum = loss_sum; a.sum_state = sum_state;
   return launch_fwd_bwd(a, as_stream(stream));
+}
+
+size_t ssnt_fwd_bwd_band_workspace_size(int batch, int max_steps, int band_width) {
+  return fwd_bwd_band_workspace_bytes(batch, max_steps, band_width);  // (0 for a shape the call refuses)
+}
+
+int ssnt_fwd_bwd_band_device(const float* log_trans_band, const float* log_obs_band,
+                             const int* band_start, const int* step_len, const int* pos_len,
+                             int batch, int max_steps, int band_width, int flags, float* loss,
+                             float* grad_band, float* grad_obs_band, void* workspace,
+                             size_t workspace_bytes, int* status, void* stream) {
+  FwdBwdBandArgs a{};
+  a.log_trans = log_trans_band; a.log_obs = log_obs_band; a.band_start = band_start;
+  a.step_len = step_len; a.pos_len = pos_len;
+  a.B = batch; a.T = max_steps; a.R = band_width; a.flags = flags;
+  a.loss = loss; a.grad = grad_band; a.grad_obs = grad_obs_band;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  return launch_fwd_bwd_band(a, as_stream(stream));
 }
 
 size_t ssnt_viterbi_align_workspace_size(int batch, int max_steps, int max_pos) {

@@ -16,6 +16,7 @@ constexpr int kStatusBadLength = 1 << 2;         // fwd-bwd: step/pos length out
 constexpr int kStatusBadIndex = 1 << 3;          // backtrace: branch index outside [0, W)
 constexpr int kStatusTimeout = 1 << 4;           // fwd-bwd: an intra-workgroup wait hit its bound
 constexpr int kStatusRingTag = 1 << 5;           // diagnostic builds only: a ring slot / row held another row
+constexpr int kStatusBadBand = 1 << 6;           // banded fwd-bwd: band_start is not a valid band
 
 int status_bits_to_code(int bits);
 
@@ -82,6 +83,26 @@ int diag_read(void* host, size_t bytes);  // -DSSNT_DIAG builds only (tools/diag
 // name per launch of a multi-launch kernel, joined by '+'); for bench.py's profile check
 void note_fwd_bwd_dispatch(const char* fmt, ...);
 const char* last_fwd_bwd_dispatch();
+
+// ---- forward-backward on a band of the emit/shift lattice (fwd_bwd_band.hip) ----
+struct FwdBwdBandArgs {
+  const float* log_trans;  // (B,T,R,2): band cell (s,r) is lattice cell (s, band_start[b,s] + r)
+  const float* log_obs;    // (B,T,R) or null
+  const int* band_start;   // (B,T): first column of every step's window
+  const int* step_len;     // (B)
+  const int* pos_len;      // (B)
+  int B, T, R, flags;      // R: band width, 1..256
+  float* loss;       // (B)
+  float* grad;       // (B,T,R,2) or null
+  float* grad_obs;   // (B,T,R) or null (requires log_obs)
+  void* workspace;   // row storage when the rows do not fit LDS; gradients only
+  size_t workspace_bytes;
+  int* status;
+};
+// the head of the kernel's LDS, then the rows of both directions when they fit; else workspace_bytes
+RowsPlan band_plan(int B, int T, int R);
+size_t fwd_bwd_band_workspace_bytes(int B, int T, int R);
+int launch_fwd_bwd_band(const FwdBwdBandArgs& a, hipStream_t stream);
 
 // ---- exact best path on the emit/shift lattice (viterbi.hip) ----
 struct ViterbiArgs {

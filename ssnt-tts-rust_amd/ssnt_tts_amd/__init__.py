@@ -5,7 +5,10 @@ The function names, argument order and meaning mirror the reference's Python op 
 130), over torch device tensors instead of TF graph tensors. Every call goes through the C ABI
 of ``lib/libssnt_tts_c.so`` (include/ssnt_tts_c.h) on torch's current HIP stream; there is no CPU
 fallback. Added beside them: the lattice forward-backward (``ssnt_fwd_bwd``,
-``SSNTLatticeLoss``), the exact best path over the same lattice (``ssnt_viterbi_align``),
+``SSNTLatticeLoss``), the same on a band of R columns per step in O(T*R) work and memory
+(``ssnt_fwd_bwd_band``, ``SSNTBandLatticeLoss``, ``ssnt_band_lattice_loss``, with the pure-torch
+helpers ``ssnt_band_from_positions``, ``ssnt_band_gather`` and ``ssnt_band_scatter``),
+the exact best path over the same lattice (``ssnt_viterbi_align``),
 the exact N best alignments (``ssnt_nbest_align``), alignments drawn from its posterior
 (``ssnt_sample_align``), the posterior expectation of an additive path cost with its gradients
 (``ssnt_expected_cost``, ``SSNTExpectedCost``, ``ssnt_alignment_entropy``), the posterior
@@ -36,6 +39,8 @@ __all__ = [
     "order_beam_branch", "upsample_source_indexes", "tone_latent_beam_search_decode",
     "levenshtein_edit_distance", "ssnt_fwd_bwd", "ssnt_viterbi_align", "ssnt_sample_align",
     "ssnt_nbest_align", "SSNTLatticeLoss",
+    "ssnt_fwd_bwd_band", "SSNTBandLatticeLoss", "ssnt_band_lattice_loss",
+    "ssnt_band_from_positions", "ssnt_band_gather", "ssnt_band_scatter",
     "ssnt_expected_cost", "SSNTExpectedCost", "ssnt_expected_cost_loss", "ssnt_alignment_entropy",
     "ssnt_lattice_loss", "ssnt_duration_posterior", "ssnt_duration_class_targets",
     "lattice_beam_search_decode", "v2_lattice_beam_search_decode",
@@ -528,6 +533,171 @@ def ssnt_lattice_loss(log_trans, step_len, pos_len, log_obs=None, terminal_emit=
                       zero_infinity=False, check=True):
     return SSNTLatticeLoss.apply(log_trans, step_len, pos_len, log_obs, terminal_emit,
                                  zero_infinity, check)
+
+
+# ----------------------------------------------------------------------------------------------
+# Forward-backward on a band of the emit/shift lattice
+# ----------------------------------------------------------------------------------------------
+def _band_start(band_start, B, T):
+    """band_start as a checked (B,T) integer tensor (int32 where it is not one already)."""
+    if not isinstance(band_start, torch.Tensor):
+        raise TypeError("band_start: expected a torch.Tensor")
+    if band_start.dtype.is_floating_point or band_start.dtype.is_complex or band_start.dtype == torch.bool:
+        raise TypeError(f"band_start must be an integer tensor, not {band_start.dtype}")
+    if tuple(band_start.shape) != (B, T):
+        raise ValueError(f"band_start must be (B,T) = {(B, T)}, not {tuple(band_start.shape)}")
+    return band_start
+
+
+def _band_index(band_start, width, U):
+    """(idx (B,T,R) int64 clamped into [0, U), inside (B,T,R) bool) of a band's columns."""
+    if int(width) < 1:
+        raise ValueError("width must be at least 1")
+    r = torch.arange(int(width), device=band_start.device, dtype=torch.int64)
+    idx = band_start.to(torch.int64)[:, :, None] + r
+    inside = (idx >= 0) & (idx < U)
+    return idx.clamp(0, max(U - 1, 0)), inside
+
+
+def ssnt_band_from_positions(position, step_len, pos_len, width):
+    """The band of `width` columns centred on an alignment (pure torch, any device).
+
+    position (B,T) integer, the input position of every step (``ssnt_viterbi_align``'s
+    ``position``; entries at steps >= S_b are not read); step_len / pos_len (B,). Returns
+    band_start (B,T) i32 with ``band_start[s] = clamp(position[s] - width//2, 0,
+    max(P - width, 0))`` and the value of step S-1 repeated beyond it. For a monotone alignment
+    (position[0] = 0, steps of 0 or 1, position[S-1] = P-1) the band is valid for
+    ``ssnt_fwd_bwd_band`` and contains the alignment."""
+    if not isinstance(position, torch.Tensor) or position.dim() != 2:
+        raise ValueError("position must be a (B,T) tensor")
+    if position.dtype.is_floating_point or position.dtype == torch.bool:
+        raise TypeError(f"position must be an integer tensor, not {position.dtype}")
+    if int(width) < 1:
+        raise ValueError("width must be at least 1")
+    B, T = position.shape
+    dev = position.device
+    S = torch.as_tensor(step_len, device=dev).reshape(B).to(torch.int64).clamp(0, T)
+    P = torch.as_tensor(pos_len, device=dev).reshape(B).to(torch.int64)
+    hi = (P - int(width)).clamp_min(0)[:, None]
+    bs = torch.minimum((position.to(torch.int64) - int(width) // 2).clamp_min(0), hi)
+    if T > 0:
+        step = torch.minimum(torch.arange(T, device=dev)[None, :], (S - 1).clamp_min(0)[:, None])
+        bs = bs.gather(1, step)
+    return bs.to(torch.int32)
+
+
+def ssnt_band_gather(dense, band_start, width, fill):
+    """Cut a band out of a dense lattice tensor (pure torch, any device): dense (B,T,U,...) ->
+    (B,T,width,...) with out[b,s,r] = dense[b,s,band_start[b,s]+r], and `fill` where that column
+    lies outside [0, U)."""
+    if not isinstance(dense, torch.Tensor) or dense.dim() < 3:
+        raise ValueError("dense must be (B,T,U,...)")
+    B, T, U = dense.shape[:3]
+    bs = _band_start(band_start, B, T)
+    idx, inside = _band_index(bs, width, U)
+    tail = dense.shape[3:]
+    shape = idx.shape + (1,) * len(tail)
+    if U == 0:
+        return torch.full(idx.shape + tail, fill, dtype=dense.dtype, device=dense.device)
+    out = dense.gather(2, idx.reshape(shape).expand(idx.shape + tail))
+    return torch.where(inside.reshape(shape), out, torch.full((), fill, dtype=dense.dtype, device=dense.device))
+
+
+def ssnt_band_scatter(band, band_start, U, fill=0):
+    """The inverse of ``ssnt_band_gather`` (pure torch, any device): band (B,T,R,...) ->
+    (B,T,U,...) with out[b,s,band_start[b,s]+r] = band[b,s,r] and `fill` outside the band; band
+    columns outside [0, U) are dropped."""
+    if not isinstance(band, torch.Tensor) or band.dim() < 3:
+        raise ValueError("band must be (B,T,R,...)")
+    B, T, R = band.shape[:3]
+    U = int(U)
+    if U < 0:
+        raise ValueError("U must not be negative")
+    bs = _band_start(band_start, B, T)
+    tail = band.shape[3:]
+    out = torch.full((B, T, U + 1) + tail, fill, dtype=band.dtype, device=band.device)
+    if R > 0:
+        idx, inside = _band_index(bs, R, U)
+        idx = torch.where(inside, idx, torch.full_like(idx, U))  # outside: the spare column
+        shape = idx.shape + (1,) * len(tail)
+        out.scatter_(2, idx.reshape(shape).expand(idx.shape + tail), band)
+    return out[:, :, :U].contiguous()
+
+
+def ssnt_fwd_bwd_band(log_trans_band, band_start, step_len, pos_len, log_obs_band=None, *,
+                      terminal_emit=True, zero_infinity=False, need_grad=True, check=False,
+                      out=None):
+    """Forward-backward over a band of the emit/shift lattice: work and memory
+    O(T*R), the dense (B,T,U,2) tensor is never formed.
+
+    log_trans_band (B,T,R,2) f32 and log_obs_band (B,T,R) (optional) hold band cell (s,r) =
+    lattice cell (s, band_start[b,s] + r); band_start (B,T) integer; step_len S_b <= T; pos_len
+    P_b (there is no U). A valid band has band_start[b,0] = 0, steps of 0 or 1 up to S_b - 1, and
+    band_start[b,S_b-1] <= P_b - 1 < band_start[b,S_b-1] + R (``ssnt_band_from_positions`` makes
+    one from an alignment; ``ssnt_band_gather`` / ``ssnt_band_scatter`` move tensors between the
+    two layouts). R in [1, 256]. Returns a dict with ``loss`` (B,) = -ln of the mass of the paths
+    inside the band, ``grad`` (B,T,R,2) and ``grad_obs`` (B,T,R) (with need_grad; the latter if
+    log_obs_band is given) and ``status``: the bits of ``ssnt_fwd_bwd`` on the dense lattice that
+    is -inf outside the band. Edges that leave the band have gradient 0 and are never read. An
+    invalid band makes its utterance infeasible (loss +inf, or 0 with zero_infinity; gradients 0)
+    and raises ``SsntError`` (SSNT_ERR_BAD_BAND) with ``check=True``. ``need_grad=False`` needs no
+    workspace and returns the same ``loss`` bits. ``out`` may pass preallocated tensors under the
+    same keys."""
+    lib = load(require_gpu=True)
+    lt = _dev(log_trans_band, torch.float32, "log_trans_band")
+    if lt.dim() != 4 or lt.shape[3] != 2:
+        raise ValueError("log_trans_band must be (B,T,R,2)")
+    B, T, R, _ = lt.shape
+    bs = _dev(_band_start(band_start, B, T), torch.int32, "band_start")
+    sl = _shaped(step_len, torch.int32, "step_len", (B,))
+    pl = _shaped(pos_len, torch.int32, "pos_len", (B,))
+    lo = None
+    if log_obs_band is not None:
+        lo = _dev(log_obs_band, torch.float32, "log_obs_band")
+        if tuple(lo.shape) != (B, T, R):
+            raise ValueError(f"log_obs_band must be (B,T,R) = {(B, T, R)}")
+    flags = (FLAG_TERMINAL_EMIT if terminal_emit else 0) | (FLAG_ZERO_INFINITY if zero_infinity else 0)
+    c = _Call("ssnt_fwd_bwd_band", lt.device, out, check)
+    loss = c.buf("loss", (B,))
+    grad = c.buf("grad", (B, T, R, 2), want=need_grad)
+    gobs = c.buf("grad_obs", (B, T, R), want=need_grad and lo is not None)
+    if need_grad:
+        c.workspace(lib.ssnt_fwd_bwd_band_workspace_size, B, T, R)
+    return c.run(lib.ssnt_fwd_bwd_band_device, lt.data_ptr(), _a(lo), bs.data_ptr(), sl.data_ptr(),
+                 pl.data_ptr(), B, T, R, flags, loss, grad, gobs)
+
+
+class SSNTBandLatticeLoss(torch.autograd.Function):
+    """Autograd wrapper of ``ssnt_fwd_bwd_band``: per-utterance loss (B,), gradients in the band
+    layout, computed in the same kernel launch. The status word (bad lengths, an invalid band) is
+    checked in backward, where the step synchronises anyway (check=False skips it)."""
+
+    @staticmethod
+    def forward(ctx, log_trans_band, band_start, step_len, pos_len, log_obs_band=None,
+                terminal_emit=True, zero_infinity=False, check=True):
+        need = log_trans_band.requires_grad or (log_obs_band is not None and log_obs_band.requires_grad)
+        r = ssnt_fwd_bwd_band(log_trans_band.detach(), band_start, step_len, pos_len,
+                              None if log_obs_band is None else log_obs_band.detach(),
+                              terminal_emit=terminal_emit, zero_infinity=zero_infinity, need_grad=need)
+        ctx.save_for_backward(r.get("grad"), r.get("grad_obs"), r["status"])
+        ctx.check = check
+        return r["loss"]
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        g, go, st = ctx.saved_tensors
+        if ctx.check:
+            _finish("ssnt_band_lattice_loss", 0, st, True)
+        gl = grad_loss.to(torch.float32)
+        gt = None if g is None else g * gl[:, None, None, None]
+        gobs = None if go is None else go * gl[:, None, None]
+        return gt, None, None, None, gobs, None, None, None
+
+
+def ssnt_band_lattice_loss(log_trans_band, band_start, step_len, pos_len, log_obs_band=None,
+                           terminal_emit=True, zero_infinity=False, check=True):
+    return SSNTBandLatticeLoss.apply(log_trans_band, band_start, step_len, pos_len, log_obs_band,
+                                     terminal_emit, zero_infinity, check)
 
 
 def ssnt_expected_cost(log_trans, cost, step_len, pos_len, log_obs=None, *, terminal_emit=True,

@@ -48,6 +48,9 @@ SIGNATURES = {
     "ssnt_fwd_bwd_debug64_device": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P,
                                             P, P, c_size_t, P, P]),
     "ssnt_fwd_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    "ssnt_fwd_bwd_band_workspace_size": (c_size_t, [c_int, c_int, c_int]),
+    "ssnt_fwd_bwd_band_device": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P,
+                                         c_size_t, P, P]),
     "ssnt_viterbi_align_workspace_size": (c_size_t, [c_int, c_int, c_int]),
     "ssnt_viterbi_align_device": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P,
                                           c_size_t, P, P]),
