@@ -24,17 +24,24 @@
 // other instruction lives on another wave. That count includes the chain's counter polls, so
 // they are kept short (stream_dev.h: Ctl, first_missing). In the disassembly of the product
 // instance (K=2, no obs), per chain:
-//   step     23 instructions before the cut: 20 VALU (two of them the storage address: the
+//   step     20 instructions before the cut: 17 VALU (two of them the storage address: the
 //            compiler re-forms stride << 3 every step), 2 ds_read_b128 of factors, 1
 //            ds_write_b128 of the row; plus 2 s_waitcnt and one address add for the factors'
-//            second element block. (One VALU fewer with a precomputed byte stride: no gain
-//            measured)
+//            second element block. The step ends v_pk_add_f32, ds_write_b128: rows are planar
+//            within the lane's slice (stream_dev.h: srow_pack), so the packed add's result pair
+//            is the store's first register pair. (23 with interleaved rows: two v_mov_b32 and
+//            an s_nop between the add and the store. One VALU fewer with a precomputed byte
+//            stride: no gain measured)
 //   poll      8: address move, one ds_read_b128 of the direction's counters, s_waitcnt,
 //            v_min3_i32, s_nop, v_readfirstlane, s_cmp, branch. (22 when each counter was a
 //            count read with its own ds_read_b32 / s_waitcnt / v_readfirstlane and scaled to a
 //            row number with s_mul + s_add before the minimum; 28 with four counters.)
 //   publish   6: two ds_write_b32 (chain, sread). (5 as one ds_write_b64 of an adjacent pair:
 //            no gain measured)
+// and per converter row (fast path, forward): ~90 instructions, 7 SALU of them the row address
+// (test, two selects, shift, 64-bit add, descriptor word 1), stepped by a constant stride; 100
+// and 17 when the address was formed from the row number (DESIGN.md 5.1 for what was tried on
+// the rest of the row).
 // Before the cut a chain polls the converters once per 4 steps; after it, the converters and
 // the gradient waves once per 2 steps: up to 5.5 instructions per step before, 25 after, with
 // the long polls, 2 and 8.5 with the short ones. Measured effect: DESIGN.md 5.1.
@@ -156,7 +163,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
       lds_xrow_st<K>(act ? rows + (size_t)s * Up + p0 : reinterpret_cast<xf*>(junk_lane), r);
     } else {
       float v[2 * K];
-      xrow_pack<K>(r, v);
+      srow_pack<K>(r, v);
       buf_st<2 * K>(v, brsrc(rows + (size_t)s * Up, Up * 8u), p0 * 8);
     }
   };
@@ -166,7 +173,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
     } else {
       float v[2 * K];
       buf_ld<2 * K>(v, brsrc(rows + (size_t)s * Up, Up * 8u), pr * 8);
-      return xrow_unpack<K>(v);
+      return srow_unpack<K>(v);
     }
   };
   // converted-input slot j of direction d: per position (E.m, E.e, X.m, X.e); obs block after
@@ -423,21 +430,35 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
     const unsigned tag0 = (d == 0 && c == 0 && b == 0 && a.loss_sum) ? sum_tag(a) : 0u;
     const int chain_end = d == 0 ? S - 1 : S;
     unsigned char* ring = inr + (size_t)d * R * slot_bytes;
-    auto load = [&](int r, Item<K, OBS>& it) {
-      const int row = min(max(d == 0 ? r : S - 1 - r, 0), T - 1);
-      gld<K, 2, NV>(it.lt, brsrc(lt + (size_t)row * U * 2, U * 8u), p0);
-      if constexpr (OBS) {
-        const int orow = min(row + 1, T - 1);
-        gld<K, 1, NV>(it.ob, brsrc(lo + (size_t)orow * U, U * 4u), p0);
+    const int nmine = (S - c + kNC - 1) / kNC;  // my stream rows: c, c + kNC, ...
+    // The loads walk this wave's rows in order, so the row address is stepped by a constant
+    // signed stride, not formed from the row number (a 64-bit multiply and a clamp per row
+    // before). The walk stops on the wave's last stream row: the prefetches past it, whose data
+    // nobody converts, read that row again, so every address stays inside rows [0, S) of this
+    // utterance. The descriptor still spans one row (lanes past U read 0).
+    const int row0 = d == 0 ? min(c, S - 1) : max(S - 1 - c, 0);
+    const ptrdiff_t rstep = d == 0 ? kNC : -kNC;
+    const float* ltp = lt + (size_t)row0 * U * 2;
+    const float* lop = OBS ? lo + (size_t)(row0 + 1) * U : nullptr;  // obs[row + 1], unclamped
+    int orow = row0 + 1;
+    int steps = max(nmine, 1) - 1;  // steps left before the last row
+    auto load = [&](Item<K, OBS>& it) {
+      gld<K, 2, NV>(it.lt, brsrc(ltp, U * 8u), p0);
+      const bool go_on = steps > 0;
+      --steps;
+      ltp += go_on ? rstep * U * 2 : 0;
+      if constexpr (OBS) {  // obs[min(row + 1, T - 1)]: row + 1 reaches T only on row T - 1
+        gld<K, 1, NV>(it.ob, brsrc(orow < T ? lop : lop - U, U * 4u), p0);
+        lop += go_on ? rstep * U : 0;
+        orow += go_on ? (int)rstep : 0;
       }
     };
     Item<K, OBS> pf[D];
 #pragma unroll
-    for (int i = 0; i < D; ++i) load(c + kNC * i, pf[i]);
+    for (int i = 0; i < D; ++i) load(pf[i]);
     int seen_chain = 0;
     const int hb = d == 0 ? M : S - M;  // first stream row the gradient waves read
     int seen_grad = hb;
-    const int nmine = (S - c + kNC - 1) / kNC;  // my stream rows: c, c + kNC, ...
     for (int base = 0; base < nmine; base += D) {
 #pragma unroll
       for (int i = 0; i < D; ++i) {
@@ -499,7 +520,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
             st_vec<4>(reinterpret_cast<float*>(act ? sl + (size_t)q * nl16 + 16 * lane : junk_lane + 16 * q), v + 4 * q);
           if constexpr (OBS) {
             float o[2 * K];
-            xrow_pack<K>(O, o);
+            srow_pack<K>(O, o);
             st_vec<2 * K>(reinterpret_cast<float*>(act ? sl + 16 * Up + 8 * p0 : junk_lane), o);
           }
 #ifdef SSNT_DIAG
@@ -513,7 +534,7 @@ __global__ __launch_bounds__(64 * (2 + 2 * kNC + 2 * kNH)) void k_fwd_bwd_stream
         }
         // refill after the old item is consumed: same registers, no copy (a copy of a register
         // with a load in flight would wait for the load)
-        load(c + kNC * (k + D), pf[i]);
+        load(pf[i]);  // row c + kNC * (k + D)
       }
     }
     dg.flush(b, role.slot);

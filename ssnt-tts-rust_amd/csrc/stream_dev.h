@@ -275,16 +275,41 @@ __device__ __forceinline__ XRow<K> xrow_zero() {
   return r;
 }
 
+// Rows of this kernel (storage rows, cut buffer, chain-row rings, the ring's obs block) are planar
+// within a lane's slice of K positions: (m0..m{K-1}, e0..e{K-1}), not xrow_pack's interleaved
+// (m0, e0, m1, e1, ...). The chains form their mantissas with packed adds, whose result register
+// pairs are then the store's operands as they stand (interleaved cost two moves and a nop per
+// step at K = 2). Every access is a whole slice at a multiple of K positions, so only this pair
+// knows the order.
+template <int K>
+__device__ __forceinline__ void srow_pack(const XRow<K>& r, float* v) {
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    v[j] = r.m[j];
+    v[K + j] = __builtin_bit_cast(float, r.e[j]);
+  }
+}
+template <int K>
+__device__ __forceinline__ XRow<K> srow_unpack(const float* v) {
+  XRow<K> r;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    r.m[j] = v[j];
+    r.e[j] = __builtin_bit_cast(int, v[K + j]);
+  }
+  return r;
+}
+
 template <int K>
 __device__ __forceinline__ XRow<K> lds_xrow(const xf* p) {
   float v[2 * K];
   ld_vec<2 * K>(v, reinterpret_cast<const float*>(p));
-  return xrow_unpack<K>(v);
+  return srow_unpack<K>(v);
 }
 template <int K>
 __device__ __forceinline__ void lds_xrow_st(xf* p, const XRow<K>& r) {
   float v[2 * K];
-  xrow_pack<K>(r, v);
+  srow_pack<K>(r, v);
   st_vec<2 * K>(reinterpret_cast<float*>(p), v);
 }
 
