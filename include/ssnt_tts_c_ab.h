@@ -62,6 +62,12 @@ int ssnt_set_host_sync(int mode);
  * in-kernel stamps of the diagnostic build (make lib-diag; -1 elsewhere) */
 int ssnt_diag_step_clock(int enable, double *out);
 int ssnt_diag_null_launch(int reps, double *out);
+/* diagnostics of the host-pointer layer: the staging plan of the calling thread's last
+ * host-pointer call ("zero-copy", "copy" or "direct"; thread-local, returns the string's length),
+ * and the number of live per-thread host contexts in the process (a context is counted from its
+ * thread's first host-pointer call until that thread exits) */
+int ssnt_diag_host_path(char *buf, size_t len);
+int ssnt_diag_host_contexts(void);
 int ssnt_diag_read(void *host, size_t bytes);
 int ssnt_diag_decode_read(void *host, size_t bytes);
 

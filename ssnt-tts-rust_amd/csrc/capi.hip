@@ -5,7 +5,8 @@
 // only. Each call here packs its inputs into one pinned staging buffer, does
 // one H2D copy, launches the HIP kernel(s) and one D2H copy on the calling thread's own stream,
 // then synchronises. Streams and scratch are thread_local: TF calls ops from several inter-op
-// threads concurrently and the calls share nothing.
+// threads concurrently and the calls share nothing (tests/test_gpu_host_abi.py); a thread's
+// context is released when the thread exits.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -47,7 +48,21 @@ void check_ptr(const void* p, const char* fn, const char* name) {
   }
 }
 
-// Per-thread GPU context: stream, device scratch, pinned staging, status word.
+#ifdef SSNT_AB
+// A/B build: host contexts that hold a stream (ssnt_diag_host_contexts) and the staging plan of
+// the calling thread's last host-pointer call (ssnt_diag_host_path)
+std::atomic<int> g_live_ctx{0};
+thread_local const char* t_host_path = "";
+inline void note_ctx(int d) { g_live_ctx.fetch_add(d, std::memory_order_relaxed); }
+inline void note_host_path(const char* p) { t_host_path = p; }
+#else
+inline void note_ctx(int) {}
+inline void note_host_path(const char*) {}
+#endif
+
+// Per-thread GPU context: stream, device scratch, pinned staging, status word. Released when its
+// thread exits (a caller with short-lived threads would otherwise leak a stream, the scratch and
+// three pinned buffers per thread); HIP errors are ignored there.
 struct HostCtx {
   int device = -1;
   hipStream_t stream = nullptr;
@@ -60,6 +75,24 @@ struct HostCtx {
   unsigned* flag_d = nullptr;  // ... and its device address
   unsigned seq = 0;            // last completion value requested
   int* status_h = nullptr;     // direct plans: the pinned status word
+  HostCtx() = default;
+  HostCtx(const HostCtx&) = delete;
+  HostCtx& operator=(const HostCtx&) = delete;
+  ~HostCtx() { release(); }
+  // drain and free everything (HIP frees device allocations and streams from any current device)
+  void release() {
+    if (stream) {
+      (void)hipStreamSynchronize(stream);
+      (void)hipStreamDestroy(stream);
+      note_ctx(-1);
+    }
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+    if (flag_h) (void)hipHostFree(flag_h);
+    if (status_h) (void)hipHostFree(status_h);
+    device = -1; stream = nullptr; d = nullptr; dcap = 0; h = nullptr; hcap = 0; hmap = nullptr;
+    flag_h = nullptr; flag_d = nullptr; seq = 0; status_h = nullptr;
+  }
 };
 thread_local HostCtx g_ctx;
 
@@ -92,22 +125,15 @@ int ctx_ready(const char* fn, bool abort_on_error) {
     return SSNT_ERR_HIP;
   }
   if (g_ctx.device != dev) {
-    // a different device for this thread: release the old device's stream and buffers (HIP
-    // frees device allocations and streams from any current device)
-    if (g_ctx.stream) {
-      (void)hipStreamSynchronize(g_ctx.stream);
-      (void)hipStreamDestroy(g_ctx.stream);
-    }
-    if (g_ctx.d) (void)hipFree(g_ctx.d);
-    if (g_ctx.h) (void)hipHostFree(g_ctx.h);
-    if (g_ctx.flag_h) (void)hipHostFree(g_ctx.flag_h);
-    if (g_ctx.status_h) (void)hipHostFree(g_ctx.status_h);
-    g_ctx = HostCtx{};
-    g_ctx.device = dev;
+    // a different device for this thread: release the old device's stream and buffers
+    g_ctx.release();
     if (hipStreamCreateWithFlags(&g_ctx.stream, hipStreamNonBlocking) != hipSuccess) {
+      g_ctx.stream = nullptr;
       if (abort_on_error) fail(fn, "hipStreamCreate failed");
       return SSNT_ERR_HIP;
     }
+    g_ctx.device = dev;
+    note_ctx(+1);
     // the completion word of the per-step symbols: coherent (uncached) pinned memory, so a GPU
     // write of it is visible to the polling host thread without a cache flush
     void* fh = nullptr;
@@ -293,6 +319,7 @@ int stage_in(Plan& p, const char* fn, bool abort_on_error, size_t extra_device =
     }
   }
   if (!p.zero_copy) p.dbase = g_ctx.d;
+  note_host_path(p.zero_copy ? "zero-copy" : "copy");
   for (auto& s : p.in) memcpy(g_ctx.h + s.off, s.src, s.bytes);
   memset(g_ctx.h + p.status_off, 0, sizeof(int));
   size_t up_end = p.status_off + sizeof(int);
@@ -356,6 +383,14 @@ int stage_out(Plan& p, int launch_rc, const char* fn, bool abort_on_error) {
   return SSNT_OK;
 }
 
+// An error return of the direct plan: copies from or into the caller's pageable arrays may still
+// be queued, and the arrays are the caller's again once the call returns, so the stream is
+// drained first (its own result ignored: `rc` is what the caller learns).
+int direct_error(int rc) {
+  (void)hipStreamSynchronize(g_ctx.stream);
+  return rc;
+}
+
 // Direct form of stage_in / stage_out for large plans (kStreamMin; inputs only, no output init
 // contents): the device layout is the plan's; the caller's arrays are copied in place.
 int stage_in_direct(Plan& p, const char* fn, size_t extra_device) {
@@ -365,25 +400,26 @@ int stage_in_direct(Plan& p, const char* fn, size_t extra_device) {
   if (rc != SSNT_OK) return rc;
   if ((rc = status_word_ready()) != SSNT_OK) return rc;
   p.dbase = g_ctx.d;
-  if (hipMemsetAsync(g_ctx.d + p.status_off, 0, sizeof(int), g_ctx.stream) != hipSuccess) return SSNT_ERR_HIP;
+  note_host_path("direct");
+  bool ok = hipMemsetAsync(g_ctx.d + p.status_off, 0, sizeof(int), g_ctx.stream) == hipSuccess;
   for (const Slot& sl : p.in)
-    if (hipMemcpyAsync(g_ctx.d + sl.off, sl.src, sl.bytes, hipMemcpyHostToDevice, g_ctx.stream) != hipSuccess)
-      return SSNT_ERR_HIP;
+    ok = ok && hipMemcpyAsync(g_ctx.d + sl.off, sl.src, sl.bytes, hipMemcpyHostToDevice, g_ctx.stream) == hipSuccess;
+  if (!ok) return direct_error(SSNT_ERR_HIP);
   return SSNT_OK;
 }
 
 // the status word first (no output is written on an error), then every output in place
 int stage_out_direct(Plan& p, int launch_rc) {
-  if (launch_rc != SSNT_OK) return launch_rc;
+  if (launch_rc != SSNT_OK) return direct_error(launch_rc);  // (the H2D copies are queued)
   int* st_h = g_ctx.status_h;
-  if (hipMemcpyAsync(st_h, g_ctx.d + p.status_off, sizeof(int), hipMemcpyDeviceToHost, g_ctx.stream) != hipSuccess ||
-      hipStreamSynchronize(g_ctx.stream) != hipSuccess)
-    return SSNT_ERR_HIP;
+  if (hipMemcpyAsync(st_h, g_ctx.d + p.status_off, sizeof(int), hipMemcpyDeviceToHost, g_ctx.stream) != hipSuccess)
+    return direct_error(SSNT_ERR_HIP);
+  if (hipStreamSynchronize(g_ctx.stream) != hipSuccess) return SSNT_ERR_HIP;
   const int rc = status_bits_to_code(*st_h);
   if (rc != SSNT_OK) return rc;
   for (const Slot& sl : p.out)
     if (hipMemcpyAsync(sl.dst, g_ctx.d + sl.off, sl.bytes, hipMemcpyDeviceToHost, g_ctx.stream) != hipSuccess)
-      return SSNT_ERR_HIP;
+      return direct_error(SSNT_ERR_HIP);
   return hipStreamSynchronize(g_ctx.stream) == hipSuccess ? SSNT_OK : SSNT_ERR_HIP;
 }
 
@@ -783,6 +819,15 @@ int ssnt_diag_null_launch(int reps, double* out) {
   out[1] = reps ? sy / reps : 0;
   return reps;
 }
+
+// the staging plan of the calling thread's last host-pointer call that built one: "zero-copy",
+// "copy" or "direct" ("" before the first); returns its length, like ssnt_fwd_bwd_last_kernel
+int ssnt_diag_host_path(char* buf, size_t len) {
+  if (buf && len) snprintf(buf, len, "%s", t_host_path);
+  return (int)strlen(t_host_path);
+}
+// live host contexts in the process: threads that made a host-pointer call and have not exited
+int ssnt_diag_host_contexts(void) { return g_live_ctx.load(std::memory_order_relaxed); }
 
 // in-kernel stamps of the diagnostic builds (make lib-diag / lib-exp; -1 otherwise)
 int ssnt_diag_read(void* host, size_t bytes) { return diag_read(host, bytes); }

@@ -8,8 +8,6 @@
 // Rust step (and with oracle/ssnt_oracle.c) by construction.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include "decode_dev.h"
 #include "launch_util.h"
 
@@ -193,6 +191,10 @@ __global__ __launch_bounds__(64) void k_levenshtein(int B, int L, const int* __r
   if (lane == 0) dist[i] = e[N];
 }
 
+// the dynamic LDS the step, upsample and edit-distance launchers accept (launch_lds raises the
+// kernels' attribute to it above 64 KiB)
+constexpr size_t kDecodeLdsCap = 150 * 1024;
+
 }  // namespace
 
 int launch_decode_step(const StepArgs& a, hipStream_t st) {
@@ -203,20 +205,8 @@ int launch_decode_step(const StepArgs& a, hipStream_t st) {
   if (a.B == 0) return SSNT_OK;
   const size_t n = (size_t)a.W * a.C;
   const size_t lds = n * sizeof(Cand) + 2 * n * sizeof(int);
-  if (lds > 150 * 1024) return SSNT_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024) {  // (the attribute is per device: set once per device, not per call)
-    static std::atomic<unsigned long long> set_on{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(set_on.load(std::memory_order_relaxed) & bit)) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_decode_step),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      set_on.fetch_or(bit);
-    }
-  }
-  hipLaunchKernelGGL(k_decode_step, dim3(a.B), dim3(64), lds, st, a);
-  return launch_status();
+  if (lds > kDecodeLdsCap) return SSNT_ERR_UNSUPPORTED;
+  return launch_lds(k_decode_step, dim3(a.B), dim3(64), lds, kDecodeLdsCap, st, a);
 }
 
 int launch_extract_best(int B, int W, int U, const int* best_final_branch, const int* beam_branch,
@@ -248,10 +238,9 @@ int launch_upsample(int B, int W, int T, int max_u, const int* duration, const i
   if (B < 0 || W <= 0 || T < 0 || max_u < 0) return SSNT_ERR_INVALID_ARG;
   if (B == 0) return SSNT_OK;
   const size_t lds = (size_t)(T + 1) * sizeof(int);
-  if (lds > 150 * 1024) return SSNT_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(k_upsample, dim3(B * W), dim3(64), lds, st, B * W, T, max_u, duration,
-                     output_length, out, status);
-  return launch_status();
+  if (lds > kDecodeLdsCap) return SSNT_ERR_UNSUPPORTED;
+  return launch_lds(k_upsample, dim3(B * W), dim3(64), lds, kDecodeLdsCap, st, B * W, T, max_u,
+                    duration, output_length, out, status);
 }
 
 int launch_levenshtein(int B, int max_length, const int* a, const int* b, const int* a_len,
@@ -259,10 +248,9 @@ int launch_levenshtein(int B, int max_length, const int* a, const int* b, const 
   if (B < 0 || max_length < 0) return SSNT_ERR_INVALID_ARG;
   if (B == 0) return SSNT_OK;
   const size_t lds = (size_t)(max_length + 1) * 2 * sizeof(int);
-  if (lds > 150 * 1024) return SSNT_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(k_levenshtein, dim3(B), dim3(64), lds, st, B, max_length, a, b, a_len,
-                     b_len, dist);
-  return launch_status();
+  if (lds > kDecodeLdsCap) return SSNT_ERR_UNSUPPORTED;
+  return launch_lds(k_levenshtein, dim3(B), dim3(64), lds, kDecodeLdsCap, st, B, max_length, a, b,
+                    a_len, b_len, dist);
 }
 
 }  // namespace ssnt

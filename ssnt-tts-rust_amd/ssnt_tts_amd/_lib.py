@@ -120,6 +120,8 @@ AB_SIGNATURES = {
     "ssnt_set_host_sync": (c_int, [c_int]),
     "ssnt_diag_step_clock": (c_int, [c_int, c_void_p]),
     "ssnt_diag_null_launch": (c_int, [c_int, c_void_p]),
+    "ssnt_diag_host_path": (c_int, [ctypes.c_char_p, c_size_t]),
+    "ssnt_diag_host_contexts": (c_int, []),
     "ssnt_diag_read": (c_int, [c_void_p, c_size_t]),
     "ssnt_diag_decode_read": (c_int, [c_void_p, c_size_t]),
 }

@@ -69,10 +69,15 @@ def ssnt_order_beam_branch(final_branch, beam_branch, batch_size, beam_width, ma
 
 
 def ssnt_upsample_source_indexes(duration, output_length, batch_size, beam_width, max_t, max_u,
-                                 fill=-1):
-    """ssnt_tts_c/src/lib.rs:245-265; `fill` plays the TF op's prefill."""
+                                 fill=-1, out=None):
+    """ssnt_tts_c/src/lib.rs:245-265; `fill` plays the TF op's prefill. `out`: the caller's own
+    prefilled (B,W,max_u) int32 array, written in place and returned (`fill` is then unused)."""
     d, ol = _a(duration, np.int32), _a(output_length, np.int32)
-    out = np.full((batch_size, beam_width, max_u), fill, np.int32)
+    if out is None:
+        out = np.full((batch_size, beam_width, max_u), fill, np.int32)
+    elif (out.dtype != np.int32 or not out.flags.c_contiguous
+          or out.shape != (batch_size, beam_width, max_u)):
+        raise ValueError("out must be a C-contiguous int32 array of shape (B, W, max_u)")
     load().ssnt_upsample_source_indexes(_p(d), _p(ol), int(batch_size), int(beam_width),
                                         int(max_t), int(max_u), _p(out))
     return out
@@ -123,3 +128,21 @@ def ssnt_fwd_bwd(log_trans, step_len, pos_len, log_obs=None, flags=1, debug=Fals
     if debug:
         out["log_alpha"], out["log_beta"] = la, lb
     return out
+
+
+def ssnt_fwd_bwd_raw(log_trans, log_obs, step_len, pos_len, batch, max_steps, max_pos, flags,
+                     loss, grad_trans, grad_obs, log_alpha, log_beta):
+    """The host-pointer entry exactly as a C caller sees it: every array argument is a numpy
+    array used in place (no conversion, no copy: a view into a larger array keeps its address) or
+    None for NULL; the sizes are passed as given; returns the status code and raises nothing."""
+    def ptr(a, dt):
+        if a is None:
+            return ctypes.c_void_p(None)
+        if a.dtype != dt or not a.flags.c_contiguous:
+            raise ValueError(f"expected a C-contiguous {np.dtype(dt).name} array")
+        return _p(a)
+    f, i = np.float32, np.int32
+    return load().ssnt_fwd_bwd(ptr(log_trans, f), ptr(log_obs, f), ptr(step_len, i), ptr(pos_len, i),
+                               int(batch), int(max_steps), int(max_pos), int(flags), ptr(loss, f),
+                               ptr(grad_trans, f), ptr(grad_obs, f), ptr(log_alpha, f),
+                               ptr(log_beta, f))

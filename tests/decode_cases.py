@@ -34,9 +34,11 @@ def v1_case(seed, B=None, W=None, max_t=None):
     return dict(h=h, hist=hist, fin=fin, t=t, u=u, input_length=il)
 
 
-def tone_case(seed):
+def tone_case(seed, B=None, W=None, C=None):
     rng = np.random.default_rng(seed + 1000)
-    B, W, C = int(rng.integers(1, 5)), int(rng.integers(1, 7)), int(rng.integers(1, 7))
+    # (the sizes are drawn even when given, so a seed's values do not depend on the arguments)
+    B0, W0, C0 = int(rng.integers(1, 5)), int(rng.integers(1, 7)), int(rng.integers(1, 7))
+    B, W, C = B or B0, W or W0, C or C0
     tie = bool(rng.integers(0, 2))
     h = _logits(rng, (B, W, C), tie)
     hist = _logits(rng, (B, W), True)

@@ -326,3 +326,125 @@ def test_v1_seven_step_reference_sequence(gpu, oracle, golden, host_sync):
                                     _t(u[None]), _t(np.array([T], np.int32)), W)
         _eq([x[0] for x in gd], want, V1_KEYS, f"device step={step}")
         hist, t, u, fin = want["log_prob"], want["next_t"], want["next_u"], want["next_is_finished"]
+
+
+# ---- dynamic LDS above 64 KiB (launch_util.h launch_lds), through the device entries only: a
+# launch the runtime refused is a status code there, while a host symbol would abort. The sizes
+# sit on both sides of 64 KiB, well above it, and one past each launcher's 150 KiB cap.
+ERR_UNSUPPORTED = 5
+
+
+@pytest.mark.parametrize("L", [8191, 8192, 12000])  # (L+1) * 8 B: 64 KiB, 64 KiB + 8, 93.8 KiB
+def test_edit_distance_lds_above_64k(gpu, oracle, L):
+    rng = np.random.default_rng(L)
+    a = rng.integers(0, 5, size=(3, L)).astype(np.int32)
+    b = rng.integers(0, 5, size=(3, L)).astype(np.int32)
+    al = np.array([L, 17, L - 3], np.int32)  # ragged: full rows, a short one, an empty one
+    bl = np.array([L, L, 0], np.int32)
+    want = oracle.levenshtein(a, b, al, bl)
+    assert want[2] == L - 3 and 0 < want[0] <= L
+    got = gpu.levenshtein_edit_distance(_t(a), _t(b), _t(al), _t(bl))
+    assert np.array_equal(got.cpu().numpy(), want), (got.cpu().numpy(), want)
+
+
+@pytest.mark.parametrize("T", [16383, 16384, 20000])  # (T+1) * 4 B: 64 KiB, 64 KiB + 4, 78.1 KiB
+def test_upsample_lds_above_64k(gpu, oracle, T):
+    rng = np.random.default_rng(T)
+    d = rng.integers(0, 6, size=(1, 2, T)).astype(np.int32)
+    d[0, 1, 100:900] = 0          # a run of skipped inputs
+    d[0, 1, T - 1] = 5            # the last input is used (the search reaches cum[T-1])
+    ol = d.sum(-1).astype(np.int32)
+    want, rc = oracle.upsample_source_indexes(d, ol, int(ol.max()))
+    assert rc == 0 and want.max() == T - 1
+    got = gpu.upsample_source_indexes(_t(d), _t(ol), -1, 2)
+    assert np.array_equal(got.cpu().numpy(), want)
+
+
+# 48 B per candidate: 96 KiB, 150 KiB (the cap); seeds whose beams are part finished, part not
+@pytest.mark.parametrize("W,C,seed", [(32, 64, 0), (50, 64, 5)])
+def test_tone_step_lds_above_64k(gpu, oracle, W, C, seed):
+    c = dc.tone_case(seed, B=2, W=W, C=C)
+    o = oracle.tone_step(c["h"], c["hist"], c["fin"], c["t"], c["u"], c["input_length"],
+                         c["empty_tone_id"])
+    g = gpu.tone_latent_beam_search_decode(_t(c["h"]), _t(c["hist"]), _t(c["fin"]), _t(c["t"]),
+                                           _t(c["u"]), _t(c["input_length"]), W, C,
+                                           c["empty_tone_id"])
+    _eq(g, o, V1_KEYS, f"W={W} C={C}")
+
+
+def test_v2_step_lds_above_64k(gpu, oracle):
+    W, D = 16, 128  # 2048 candidates, 96 KiB
+    c = dc.v2_case_long(1, W, D, B=2)
+    ol = np.zeros_like(c["output_length"]) if c["test_mode"] else c["output_length"]
+    o, rc = oracle.v2_step(c["h"], c["hist"], c["fin"], c["total"], c["table"], c["t"], c["u"],
+                           c["input_length"], ol, c["zero_duration_id"], c["allow_skip"],
+                           c["test_mode"])
+    assert rc == 0
+    g = gpu.ssnt_tts_v2_beam_search_decode(
+        _t(c["h"]), _t(c["hist"]), _t(c["fin"]), _t(c["total"]), _t(c["table"]), _t(c["t"]),
+        _t(c["u"]), _t(c["input_length"]), _t(c["output_length"]), W, D, c["zero_duration_id"],
+        c["allow_skip"], c["test_mode"])
+    _eq(g, o, V2_KEYS, "W=16 D=128")
+
+
+def _sentinels(*shapes_dtypes):
+    """Device tensors whose every byte is 0x5A."""
+    out = []
+    for shape, dt in shapes_dtypes:
+        n = int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
+        out.append(torch.full((n,), 0x5A, dtype=torch.uint8, device="cuda:0").view(dt).reshape(shape))
+    return out
+
+
+def _all_sentinel(t):
+    return bool((t.view(torch.uint8) == 0x5A).all().item())
+
+
+def test_lds_cap_is_unsupported_and_writes_nothing(gpu):
+    # one past each launcher's 150 KiB: SSNT_ERR_UNSUPPORTED from the device entry (SsntError with
+    # that code from the mirror), no launch, every output byte and the status word as they were
+    from gpu_util import vp
+    lib = gpu.load()
+    stream = None  # the default stream
+    # decode step: 3201 candidates x 48 B
+    W, C = 3201, 1
+    h = torch.zeros((1, W, C), device="cuda:0")
+    z = torch.zeros((1, W), dtype=torch.int32, device="cuda:0")
+    fin = torch.zeros((1, W), dtype=torch.bool, device="cuda:0")
+    il = torch.full((1,), 4, dtype=torch.int32, device="cuda:0")
+    outs = _sentinels(*[((1, W), dt) for dt in (torch.int32, torch.float32, torch.int32, torch.int32,
+                                                torch.uint8, torch.int32)])
+    (status,) = _sentinels(((1,), torch.int32))
+    rc = lib.ssnt_tone_latent_beam_search_decode_device(
+        vp(h), vp(h[..., 0].contiguous()), vp(fin), vp(z), vp(z), vp(il), 1, W, C, 0,
+        *[vp(o) for o in outs], vp(status), stream)
+    torch.cuda.synchronize()
+    assert rc == ERR_UNSUPPORTED
+    assert all(_all_sentinel(o) for o in outs) and _all_sentinel(status)
+    with pytest.raises(gpu.SsntError) as e:
+        gpu.tone_latent_beam_search_decode(h, h[..., 0], fin, z, z, il, W, C, 0)
+    assert e.value.code == ERR_UNSUPPORTED
+    # edit distance: (19200 + 1) x 8 B
+    L = 19200
+    a = torch.zeros((1, L), dtype=torch.int32, device="cuda:0")
+    ln = torch.full((1,), L, dtype=torch.int32, device="cuda:0")
+    (dist,) = _sentinels(((1,), torch.int32))
+    rc = lib.ssnt_levenshtein_edit_distance_device(vp(a), vp(a), vp(ln), vp(ln), 1, L, vp(dist),
+                                                   stream)
+    torch.cuda.synchronize()
+    assert rc == ERR_UNSUPPORTED and _all_sentinel(dist)
+    with pytest.raises(gpu.SsntError) as e:
+        gpu.levenshtein_edit_distance(a, a, ln, ln)
+    assert e.value.code == ERR_UNSUPPORTED
+    # upsample: (38400 + 1) x 4 B
+    T = 38400
+    d = torch.ones((1, 1, T), dtype=torch.int32, device="cuda:0")
+    ol = torch.full((1, 1), T, dtype=torch.int32, device="cuda:0")
+    out, status = _sentinels(((1, 1, T), torch.int32), ((1,), torch.int32))
+    rc = lib.ssnt_upsample_source_indexes_device(vp(d), vp(ol), 1, 1, T, T, vp(out), vp(status),
+                                                 stream)
+    torch.cuda.synchronize()
+    assert rc == ERR_UNSUPPORTED and _all_sentinel(out) and _all_sentinel(status)
+    with pytest.raises(gpu.SsntError) as e:
+        gpu.upsample_source_indexes(d, ol, -1, 1)
+    assert e.value.code == ERR_UNSUPPORTED

@@ -407,8 +407,9 @@ def test_host_pointer_entry(gpu, oracle):
 
 def test_host_pointer_entry_large(gpu, oracle, kernel_variant):
     # calls of 8 MB and more copy straight between the caller's pageable arrays and the device
-    # (capi.hip stage_in_direct / stage_out_direct): every output, ragged lengths, and the status
-    # word checked before any output is written
+    # (capi.hip stage_in_direct / stage_out_direct): every output, ragged lengths, and the error
+    # code of a bad length. That an error return leaves the caller's outputs untouched is checked
+    # with sentinel-filled arrays in test_gpu_host_abi.py::test_errors_leave_no_trace
     from ssnt_tts_amd import capi
     B, T, U = 97, 200, 80  # 12.4 MB of log_trans
     rng = np.random.default_rng(5)
