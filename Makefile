@@ -16,7 +16,7 @@ HIPFLAGS  := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fvisi
              -Wno-unused-function -I include -I $(CSRC)
 HIP_SRCS  := $(CSRC)/fwd_bwd_dispatch.hip $(CSRC)/fwd_bwd.hip $(CSRC)/fwd_bwd_stream.hip $(CSRC)/fwd_bwd_wide.hip $(CSRC)/fwd_bwd_band.hip $(CSRC)/v2_fwd_bwd.hip $(CSRC)/v2_viterbi.hip \
              $(CSRC)/v2_sample_align.hip $(CSRC)/v2_nbest_align.hip \
-             $(CSRC)/decode.hip $(CSRC)/viterbi.hip $(CSRC)/sample_align.hip $(CSRC)/nbest_align.hip \
+             $(CSRC)/decode.hip $(CSRC)/viterbi.hip $(CSRC)/viterbi_band.hip $(CSRC)/sample_align.hip $(CSRC)/nbest_align.hip \
              $(CSRC)/expected_cost.hip $(CSRC)/duration_posterior.hip $(CSRC)/v2_expected_cost.hip \
              $(CSRC)/fused_decode.hip $(CSRC)/capi.hip
 # the A/B and diagnostic builds compile the same sources with their own macros

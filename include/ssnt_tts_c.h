@@ -233,6 +233,38 @@ int ssnt_viterbi_align_device(const float *log_trans, const float *log_obs, cons
                               float *log_prob, int *position, int *duration, void *workspace,
                               size_t workspace_bytes, int *status, void *stream);
 
+/* ---- exact best path (Viterbi) on a band of the emit/shift lattice ----
+ * ssnt_viterbi_align_device on the lattice of ssnt_fwd_bwd_band_device: log_trans_band (B,T,R,2),
+ * log_obs_band (B,T,R) (NULL = none), band_start (B,T) i32, step_len, pos_len and the validity of a
+ * band exactly as there, band_width = R. The outputs are bit for bit those of
+ * ssnt_viterbi_align_device on the dense lattice that is the band inside it and -inf outside it and
+ * on the two kinds of band-leaving edges (a tie keeps the emit): log_prob (B) = log-probability of
+ * the best path whose every cell lies in the band (with the terminal emit under
+ * SSNT_FLAG_TERMINAL_EMIT, the only flag accepted); position (B,T) = its absolute position
+ * band_start + r at every step (-1 for steps >= S_b; NULL = skip); duration (B,max_pos) = the steps
+ * each position holds (0 for positions >= P_b; NULL = skip). max_pos only sizes duration: with
+ * duration NULL it is ignored, with duration given an utterance with P_b > max_pos is a bad length.
+ * An utterance gets log_prob -inf, positions -1 and durations 0 when S_b < P_b, S_b = 0, P_b = 0 or
+ * log_prob = -inf; for a bad length (S_b > T, a negative length, P_b > max_pos), which also sets
+ * SSNT_ERR_BAD_LENGTH in `status`; and for an invalid band, which also sets SSNT_ERR_BAD_BAND: the
+ * band is refused by comparisons alone and the other utterances are unaffected. Never read into a
+ * result: what ssnt_fwd_bwd_band_device never reads, the previous contents of the outputs and of
+ * the workspace. -inf inputs are legal. band_width outside [1, 256] and a max_steps whose staged
+ * band_start and run starts do not fit LDS (above about 16000) return SSNT_ERR_UNSUPPORTED, a flag
+ * other than SSNT_FLAG_TERMINAL_EMIT or a missing required pointer SSNT_ERR_INVALID_ARG. `workspace`
+ * holds ssnt_viterbi_align_band_workspace_size() bytes when a path is requested: 0 (NULL workspace)
+ * while the decision bits of one utterance fit LDS, else 8 bytes per step and 64 columns, 8-byte
+ * aligned; missing, short or misaligned: SSNT_ERR_WORKSPACE. With position and duration both NULL
+ * no decision bits are kept, no workspace is needed and log_prob has the same bits. A refused call
+ * writes nothing. Device pointers, asynchronous on `stream`. New: the reference only searches this
+ * lattice with a pruned beam. */
+size_t ssnt_viterbi_align_band_workspace_size(int batch, int max_steps, int band_width);
+int ssnt_viterbi_align_band_device(const float *log_trans_band, const float *log_obs_band,
+                                   const int *band_start, const int *step_len, const int *pos_len,
+                                   int batch, int max_steps, int band_width, int max_pos, int flags,
+                                   float *log_prob, int *position, int *duration, void *workspace,
+                                   size_t workspace_bytes, int *status, void *stream);
+
 /* ---- the exact N best alignments on the emit/shift lattice ----
  * The beam search over this lattice with an unbounded beam, truncated to num_best: every cell of
  * the recurrence of ssnt_viterbi_align_device keeps the num_best best prefixes instead of one,

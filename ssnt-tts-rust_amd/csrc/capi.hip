@@ -919,6 +919,24 @@ int ssnt_viterbi_align_device(const float* log_trans, const float* log_obs, cons
   return launch_viterbi(a, as_stream(stream));
 }
 
+size_t ssnt_viterbi_align_band_workspace_size(int batch, int max_steps, int band_width) {
+  return viterbi_band_workspace_bytes(batch, max_steps, band_width);  // (0 for a shape the call refuses)
+}
+
+int ssnt_viterbi_align_band_device(const float* log_trans_band, const float* log_obs_band,
+                                   const int* band_start, const int* step_len, const int* pos_len,
+                                   int batch, int max_steps, int band_width, int max_pos, int flags,
+                                   float* log_prob, int* position, int* duration, void* workspace,
+                                   size_t workspace_bytes, int* status, void* stream) {
+  ViterbiBandArgs a{};
+  a.log_trans = log_trans_band; a.log_obs = log_obs_band; a.band_start = band_start;
+  a.step_len = step_len; a.pos_len = pos_len;
+  a.B = batch; a.T = max_steps; a.W = band_width; a.max_pos = max_pos; a.flags = flags;
+  a.log_prob = log_prob; a.position = position; a.duration = duration;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.status = status;
+  return launch_viterbi_band(a, as_stream(stream));
+}
+
 size_t ssnt_nbest_align_workspace_size(int batch, int max_steps, int max_pos, int num_best) {
   if (batch <= 0 || max_steps <= 0 || max_pos <= 0) return 0;
   return nbest_align_workspace_bytes(batch, max_steps, max_pos, num_best);

@@ -121,6 +121,24 @@ struct ViterbiArgs {
 size_t viterbi_workspace_bytes(int B, int T, int U);
 int launch_viterbi(const ViterbiArgs& a, hipStream_t stream);
 
+// ---- exact best path on a band of the emit/shift lattice (viterbi_band.hip) ----
+struct ViterbiBandArgs {
+  const float* log_trans;  // (B,T,W,2): band cell (s,r) is lattice cell (s, band_start[b,s] + r)
+  const float* log_obs;    // (B,T,W) or null
+  const int* band_start;   // (B,T): first column of every step's window
+  const int* step_len;     // (B)
+  const int* pos_len;      // (B)
+  int B, T, W, max_pos, flags;  // W: band width, 1..256; max_pos sizes duration only
+  float* log_prob;   // (B)
+  int* position;     // (B,T) or null: absolute positions
+  int* duration;     // (B,max_pos) or null
+  void* workspace;   // decision words when they do not fit LDS; paths only
+  size_t workspace_bytes;
+  int* status;
+};
+size_t viterbi_band_workspace_bytes(int B, int T, int W);
+int launch_viterbi_band(const ViterbiBandArgs& a, hipStream_t stream);
+
 // ---- the exact N best alignments on the emit/shift lattice (nbest_align.hip) ----
 struct NbestAlignArgs {
   const float* log_trans;  // (B,T,U,2)

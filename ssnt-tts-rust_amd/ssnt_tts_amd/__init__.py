@@ -8,7 +8,8 @@ fallback. Added beside them: the lattice forward-backward (``ssnt_fwd_bwd``,
 ``SSNTLatticeLoss``), the same on a band of R columns per step in O(T*R) work and memory
 (``ssnt_fwd_bwd_band``, ``SSNTBandLatticeLoss``, ``ssnt_band_lattice_loss``, with the pure-torch
 helpers ``ssnt_band_from_positions``, ``ssnt_band_gather`` and ``ssnt_band_scatter``),
-the exact best path over the same lattice (``ssnt_viterbi_align``),
+the exact best path over the same lattice (``ssnt_viterbi_align``) and inside a band of it
+(``ssnt_viterbi_align_band``, with ``ssnt_band_edge_contact`` to tell a band that is too narrow),
 the exact N best alignments (``ssnt_nbest_align``), alignments drawn from its posterior
 (``ssnt_sample_align``), the posterior expectation of an additive path cost with its gradients
 (``ssnt_expected_cost``, ``SSNTExpectedCost``, ``ssnt_alignment_entropy``), the posterior
@@ -41,6 +42,7 @@ __all__ = [
     "ssnt_nbest_align", "SSNTLatticeLoss",
     "ssnt_fwd_bwd_band", "SSNTBandLatticeLoss", "ssnt_band_lattice_loss",
     "ssnt_band_from_positions", "ssnt_band_gather", "ssnt_band_scatter",
+    "ssnt_viterbi_align_band", "ssnt_band_edge_contact",
     "ssnt_expected_cost", "SSNTExpectedCost", "ssnt_expected_cost_loss", "ssnt_alignment_entropy",
     "ssnt_lattice_loss", "ssnt_duration_posterior", "ssnt_duration_class_targets",
     "lattice_beam_search_decode", "v2_lattice_beam_search_decode",
@@ -665,6 +667,77 @@ def ssnt_fwd_bwd_band(log_trans_band, band_start, step_len, pos_len, log_obs_ban
         c.workspace(lib.ssnt_fwd_bwd_band_workspace_size, B, T, R)
     return c.run(lib.ssnt_fwd_bwd_band_device, lt.data_ptr(), _a(lo), bs.data_ptr(), sl.data_ptr(),
                  pl.data_ptr(), B, T, R, flags, loss, grad, gobs)
+
+
+def ssnt_viterbi_align_band(log_trans_band, band_start, step_len, pos_len, log_obs_band=None, *,
+                            terminal_emit=True, need_path=True, max_pos=None, check=False, out=None):
+    """Exact best path (Viterbi) inside a band of the emit/shift lattice: work
+    and memory O(T*R), the dense (B,T,U,2) tensor is never formed.
+
+    Inputs as ``ssnt_fwd_bwd_band``. Returns a dict with ``log_prob`` (B,) f32, the
+    log-probability of the most probable alignment whose every cell lies in the band;
+    ``position`` (B,T) i32 (with need_path), its absolute position ``band_start + r`` at every
+    step (-1 for steps >= S_b), which ``ssnt_band_from_positions`` turns into the next band;
+    ``duration`` (B,max_pos) i32 (with need_path and ``max_pos`` given), the steps each position
+    holds; ``status``: the bits of ``ssnt_viterbi_align`` on the dense lattice that is -inf
+    outside the band. An infeasible utterance gets -inf, -1 and 0; so does an utterance with an
+    invalid band (SSNT_ERR_BAD_BAND with ``check=True``) or with P_b > max_pos
+    (SSNT_ERR_BAD_LENGTH). ``need_path=False`` needs no workspace and returns the same
+    ``log_prob`` bits. ``ssnt_band_edge_contact`` tells whether the band was too narrow. ``out``
+    may pass preallocated tensors under the same keys."""
+    lib = load(require_gpu=True)
+    lt = _dev(log_trans_band, torch.float32, "log_trans_band")
+    if lt.dim() != 4 or lt.shape[3] != 2:
+        raise ValueError("log_trans_band must be (B,T,R,2)")
+    B, T, R, _ = lt.shape
+    bs = _dev(_band_start(band_start, B, T), torch.int32, "band_start")
+    sl = _shaped(step_len, torch.int32, "step_len", (B,))
+    pl = _shaped(pos_len, torch.int32, "pos_len", (B,))
+    lo = None
+    if log_obs_band is not None:
+        lo = _dev(log_obs_band, torch.float32, "log_obs_band")
+        if tuple(lo.shape) != (B, T, R):
+            raise ValueError(f"log_obs_band must be (B,T,R) = {(B, T, R)}")
+    if max_pos is not None and int(max_pos) < 0:
+        raise ValueError("max_pos must not be negative")
+    U = 0 if max_pos is None else int(max_pos)
+    c = _Call("ssnt_viterbi_align_band", lt.device, out, check)
+    lp = c.buf("log_prob", (B,))
+    pos = c.buf("position", (B, T), torch.int32, want=need_path)
+    dur = c.buf("duration", (B, U), torch.int32, want=need_path and max_pos is not None)
+    if need_path:
+        c.workspace(lib.ssnt_viterbi_align_band_workspace_size, B, T, R)
+    return c.run(lib.ssnt_viterbi_align_band_device, lt.data_ptr(), _a(lo), bs.data_ptr(),
+                 sl.data_ptr(), pl.data_ptr(), B, T, R, U, FLAG_TERMINAL_EMIT if terminal_emit else 0,
+                 lp, pos, dur)
+
+
+def ssnt_band_edge_contact(position, band_start, step_len, pos_len, width):
+    """How often a path touches an edge of its band that has lattice beyond it (pure torch, any
+    device): the sign that the band is too narrow.
+
+    position (B,T) integer, absolute positions (``ssnt_viterbi_align_band``'s ``position``; -1
+    marks an infeasible utterance); band_start (B,T) integer; step_len / pos_len (B,); ``width``
+    = R. Returns (B,) i32: the number of steps s < S_b at which the path sits on column r = 0 with
+    ``band_start[s] > 0``, or on column r = R-1 with ``band_start[s] + R < P_b``. 0 for an
+    infeasible utterance."""
+    if not isinstance(position, torch.Tensor) or position.dim() != 2:
+        raise ValueError("position must be a (B,T) tensor")
+    if position.dtype.is_floating_point or position.dtype == torch.bool:
+        raise TypeError(f"position must be an integer tensor, not {position.dtype}")
+    if int(width) < 1:
+        raise ValueError("width must be at least 1")
+    B, T = position.shape
+    dev = position.device
+    bs = _band_start(band_start, B, T).to(device=dev, dtype=torch.int64)
+    S = torch.as_tensor(step_len, device=dev).reshape(B).to(torch.int64).clamp(0, T)
+    P = torch.as_tensor(pos_len, device=dev).reshape(B).to(torch.int64)
+    pos = position.to(torch.int64)
+    live = (torch.arange(T, device=dev)[None, :] < S[:, None]) & (pos >= 0)
+    r = pos - bs
+    low = (r == 0) & (bs > 0)
+    high = (r == int(width) - 1) & (bs + int(width) < P[:, None])
+    return ((low | high) & live).sum(dim=1).to(torch.int32)
 
 
 class SSNTBandLatticeLoss(torch.autograd.Function):

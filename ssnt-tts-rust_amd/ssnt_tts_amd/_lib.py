@@ -54,6 +54,9 @@ SIGNATURES = {
     "ssnt_viterbi_align_workspace_size": (c_size_t, [c_int, c_int, c_int]),
     "ssnt_viterbi_align_device": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P,
                                           c_size_t, P, P]),
+    "ssnt_viterbi_align_band_workspace_size": (c_size_t, [c_int, c_int, c_int]),
+    "ssnt_viterbi_align_band_device": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P,
+                                               P, P, c_size_t, P, P]),
     "ssnt_nbest_align_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int]),
     "ssnt_nbest_align_device": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P,
                                         c_size_t, P, P]),
